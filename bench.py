@@ -20,6 +20,10 @@ The timed region is EXACTLY `--steps` steps between barrier + synchronize pairs;
 at least `--min-time` seconds have been timed and the MEDIAN region decides `value` (the spread is
 reported).  Rank 0 prints ONE JSON line with `roofline`, `cpu_baseline` and `check` (FNV-1a-64 of D1 of
 frame 0 against the reference's golden hash; a mismatch exits non-zero).
+
+`--dump-outputs DIR`: after the timed regions rank 0 writes what the LAST timed step handed its caller (the outputs of the slot that step
+ran on) as DIR/<name>.npy, float32 or float64, at most DUMP_MAX_BYTES in all.  The inputs depend on the arguments alone (seeded generator),
+so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import ctypes as C
@@ -34,7 +38,6 @@ import time
 
 import numpy as np
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before HIP initialises: one hardware queue per slot stream (see jackal_navigation_amd/__init__.py)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC (RCCL between processes)
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -61,6 +64,28 @@ def _evidence_round():
 
 PMC_FILE = os.path.join(ROOT, "profiles", "%s_pmc_traffic.json" % _evidence_round())
 KERNELS_SRC = os.path.join(ROOT, "jackal_navigation_amd", "csrc", "kernels.hip")
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: every file together, .npy headers included, stays under 64 MB
+DUMP_SEED = 12345
+
+
+def dump_outputs(directory, arrays):
+    """Writes each array of `arrays` (name -> numpy array) as directory/<name>.npy: float64 stays, everything else becomes float32 (exact
+    for the u8 / int16 outputs).  The budget is shared smallest first; an array larger than its share is written as a 1-D sample of
+    its flattened elements at sorted indices drawn without replacement from a generator seeded with DUMP_SEED — the same elements for the same
+    shapes in every run and every build.  Returns what was written, for the result line."""
+    os.makedirs(directory, exist_ok=True)
+    left, written = DUMP_MAX_BYTES, {}
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    for i, (name, arr) in enumerate(todo):
+        out = np.ascontiguousarray(arr, dtype=np.float64 if arr.dtype == np.float64 else np.float32)
+        keep = (left // (len(todo) - i) - 256) // out.itemsize
+        if out.size > keep:
+            out = out.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).choice(out.size, size=keep, replace=False))]
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, out)
+        left -= os.path.getsize(path)
+        written[name] = {"shape": list(arr.shape), "dtype": str(out.dtype), "elements_written": int(out.size), "sampled": out.size != arr.size}
+    return {"dir": directory, "seed": DUMP_SEED, "arrays": written}
 
 
 def cpu_baseline_worker(args):
@@ -124,6 +149,9 @@ def parse_args():
     ap.add_argument("--host-threads", type=int, default=0)
     ap.add_argument("--min-time", type=float, default=1.0, help="repeat the timed region until this many seconds have been timed")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, under 64 MB in all; "
+                         "large arrays as a fixed seeded sample of their elements)")
     ap.add_argument("--no-latency-config", action="store_true",
                     help="skip the informational 640x480 batch-1 leg (profiles then hold the headline workload's launches only)")
     ap.add_argument("--no-alone-leg", action="store_true", help="skip the un-pipelined leg that times k_dense_row running alone")
@@ -415,6 +443,10 @@ def run_sgm(a):
         regions.append(region())
     elapsed = float(np.median(regions))
     value = world * B * a.steps / elapsed
+    dumped = None
+    if a.dump_outputs and rank == 0:                         # the slot of the last timed step, before any other leg writes to it
+        od, ou, ob, om = slot_out[(step.count - 1) % SS]
+        dumped = dump_outputs(a.dump_outputs, {"disparity": od.cpu().numpy(), "disparity_u8": ou.cpu().numpy(), "scan_bins": ob.cpu().numpy(), "scan_meta": om.cpu().numpy()})
     if bm and SS > 1:                                        # the kernels' own durations for the roofline: a few batches alone, outside the timed regions
         acc.clear()
         for i in range(10):
@@ -472,6 +504,8 @@ def run_sgm(a):
                           "parallelism": "rigs sharded 1 batch/GPU over %d ranks" % world if world > 1 else "single GPU"},
                "timing": {"regions": len(regions), "region_s_median": round(elapsed, 5), "region_s_min": round(min(regions), 5), "region_s_max": round(max(regions), 5)},
                "stage_ms_per_batch": {k: round(v, 3) for k, v in ms.items()}, "roofline": roofline, "cpu_baseline": cpu, "check": check}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out))
         sys.stdout.flush()
     sgm.close()
@@ -716,6 +750,11 @@ def run_rank(a):
         regions.append(timed_region())
     host_cpu = host_cpu_report(cpu0, cg0, time.perf_counter() - t_cpu0)
     elapsed = float(np.median(regions))
+    dumped = None
+    if a.dump_outputs and rank == 0:              # the slot of the last timed step, before any other leg writes to it
+        ls = (a.steps - 1) % S
+        dumped = dump_outputs(a.dump_outputs, {"D1": D1[ls].cpu().numpy(), "D2": D2[ls].cpu().numpy(), "disparity_u8": U8[ls].cpu().numpy(),
+                                               "scan_bins": bins[ls].cpu().numpy(), "scan_meta": meta[ls].cpu().numpy()})    # (the pairs' status codes: `pairs_failed` of the line)
 
     failed = sum(1 for s in status for x in s if x != 0)
     pairs = world * B * a.steps
@@ -955,7 +994,7 @@ def run_rank(a):
     if rank == 0 and world == 1 and not a.no_latency_config and a.disp in (64, 128, 256):
         other_modes = {}
         # The ELAS handle is done: it is closed before these legs.  Left open, its four slot streams keep hardware queues (the runtime
-        # has GPU_MAX_HW_QUEUES of them, 8 here), the SGM slots' streams then share queues among themselves and batches that should
+        # has GPU_MAX_HW_QUEUES of them), the SGM slots' streams then share queues among themselves and batches that should
         # overlap run one after the other: 4.37 k instead of 4.9 k pairs/s (profiles/*_hw_queues_ab.txt).
         elas.close()
         for kind in ("sgm", "bm", "bm_ssd"):
@@ -1086,6 +1125,8 @@ def run_rank(a):
         }
         if merge_report is not None:
             out["merge"] = merge_report
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if ranks_info is not None:
             out["ranks"] = ranks_info
             out["distinct_devices"] = sorted({r["device"] for r in ranks_info})

@@ -69,8 +69,8 @@ typedef struct jn_bm_times { float prefilter, match, finish, total; } jn_bm_time
 /* Several batches in flight (as jn_sgm_submit_scan / jn_sgm_wait): slot in [0, 6); each slot has its own stream, events and scratch,
  * allocated when the slot is first used (slot 0 is the synchronous calls').  jn_bm_submit_scan queues the matcher and — when sp is not
  * NULL — the mono8 map and the LUT scan on the slot's stream and returns; jn_bm_wait(slot) must precede reading the slot's outputs or
- * submitting to it again.  With sp == NULL the u8 / bins / meta pointers may be NULL (disparities only).  A process that keeps more than
- * eight streams busy should export GPU_MAX_HW_QUEUES=16. */
+ * submitting to it again.  With sp == NULL the u8 / bins / meta pointers may be NULL (disparities only).  Slots beyond the
+ * process's hardware queues (the HIP runtime's GPU_MAX_HW_QUEUES) share a queue and serialise. */
 jn_status jn_bm_submit_scan(jn_bm* h, int32_t slot, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride,
                             int16_t* dDisp, const jn_scan_params* sp, const uint8_t* dLut, uint8_t* dDispU8, double* dBins, double* dMeta);
 jn_status jn_bm_wait(jn_bm* h, int32_t slot);

@@ -164,13 +164,6 @@ int comm_device(const jn_comm* c);
 
 namespace {
 
-// Runs when the library is loaded.  The HIP runtime multiplexes streams onto 4 hardware queues by default; with one
-// stream per slot plus the caller's, two slots then share a queue and serialise.  Ask for 16 unless the user chose a
-// value (8 until round 4: enough for one four-slot handle, but a process that also runs the SGM or block-matching mode
-// with its own slots lost 10 % there, profiles/r04_hw_queues_ab.txt; 16 measured neutral for a single handle); it only
-// takes effect if the HIP runtime has not initialised yet (load this library first, or export it).
-__attribute__((constructor)) void prefer_one_queue_per_slot() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
-
 // Waiting for the GPU without burning the host's cores.  hipEventSynchronize spins on this runtime even for events created
 // with hipEventBlockingSync: the four slot workers then cost 2.5 cores of pure waiting (measured: 4.2 ms of CPU per 32-pair
 // batch), and on the GPU boxes the container's CPU quota (16 CPUs) is what the Delaunay pool needs.  So: poll the event —
@@ -894,6 +887,7 @@ jn_status jn_elas_create(const jn_elas_params* p, int32_t W, int32_t H, int32_t 
       CREATE_TRY(dmalloc(&s->d_list, B * dp.cw * dp.ch * 3)); CREATE_TRY(dmalloc(&s->d_cnt, B));
       CREATE_TRY(dmalloc(&s->d_arr, B * 2 * (size_t)h->arr_stride)); CREATE_TRY(dmalloc(&s->d_arr_ok, B * 2));
       CREATE_TRY(hipMemset(s->payload, 0, B * h->payload_cap));
+      CREATE_TRY(hipStreamSynchronize(nullptr));             // hipMemset only queues the fill, and the slot's streams do not wait for the null stream: a late fill would wipe a payload
       if (h->dt_gcap) CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&s->dt_scratch), delaunay_gpu_scratch_bytes((int)B, h->dt_gcap)));      // (a side k_delaunay hands back leaves its part unwritten: never uninitialised memory)
     }
   }

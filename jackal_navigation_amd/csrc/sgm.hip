@@ -105,7 +105,6 @@ jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t ma
     SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.volH0), z.vol));
     SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.volH1), z.vol));
     SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.gx), z.gx));
-    SGM_CREATE_TRY(hipMemset(h->sb.gx, 0, z.gx));               // tag 0 = "never written" (sgm_sweep.hip, k_sw_w)
     h->sb.gx_bytes = z.gx;
     if (const char* e = JN_HOOK_ENV("JN_SGM_EPOCH_START")) h->sb.epoch = (uint32_t)atoi(e) & 0xFFFFu;   // test hook: start next to the tag's wrap-around
     SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.flags), z.flags));
@@ -113,6 +112,9 @@ jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t ma
     SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.dl), z.dl));
   }
   SGM_CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  // tag 0 = "never written" (sgm_sweep.hip, k_sw_w).  On the stream the sweeps run on: hipMemset returns once the fill is QUEUED on the null
+  // stream, which a non-blocking stream does not wait for — a fill that runs late wipes columns a block is still waiting to read.
+  SGM_CREATE_TRY(hipMemsetAsync(h->sb.gx, 0, h->sb.gx_bytes, h->stream));
   for (auto& e : h->ev) SGM_CREATE_TRY(hipEventCreate(&e));
 #undef SGM_CREATE_TRY
   *out = h;
@@ -145,7 +147,6 @@ static jn_status sgm_ensure_slot(jn_sgm* h, int slot) {
   SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH0), z.vol));
   SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH1), z.vol));
   SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gx), z.gx));
-  SGM_TRY(hipMemset(x.sb.gx, 0, z.gx));
   x.sb.gx_bytes = z.gx;
   x.sb.epoch = h->sb.epoch;                                     // (tests start it next to the tag's wrap-around)
   SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.flags), z.flags));
@@ -160,6 +161,7 @@ static jn_status sgm_ensure_slot(jn_sgm* h, int slot) {
       x.stream = lower == 0 ? h->stream : h->extra[lower - 1].stream; x.shared = true;
     } else SGM_TRY(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
   }
+  SGM_TRY(hipMemsetAsync(x.sb.gx, 0, x.sb.gx_bytes, x.stream)); // ahead of the slot's first sweep in stream order (see jn_sgm_create)
   for (auto& e : x.ev) SGM_TRY(hipEventCreate(&e));
   x.ready = true;
   return JN_OK;
