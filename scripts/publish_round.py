@@ -63,8 +63,13 @@ for src, name in (("default_bench_line.json", "default_bench_line_under_rocprof.
                   ("host_threads.txt", None), ("pk3_probe.txt", None), ("dep_chain_probe.txt", None), ("lds_unaligned_probe.txt", None), ("op_rate_probe.txt", None),
                   ("dense_dbg_switches.txt", None), ("hw_queues_ab.txt", None), ("gate_ab.txt", None), ("lone_timeline.txt", None), ("gpu_tests.txt", None),
                   ("gpu_delaunay_ab.txt", None), ("lone_env_ab.txt", None), ("fetch_size_probe.txt", None), ("dt_no_volatile.txt", None),
-                  ("slot_timeline.txt", None), ("full_hd_routes.txt", None), ("lone_wave_probe.txt", None), ("lds_misaligned_store_probe.txt", None)):
+                  ("slot_timeline.txt", None), ("full_hd_routes.txt", None), ("lone_wave_probe.txt", None), ("lds_misaligned_store_probe.txt", None),
+                  ("matcher_kernel_coverage.txt", None), ("suite_kernel_coverage.txt", None)):
     put(os.path.join(g, "%s_%s" % (tag, src)), "%s_%s" % (tag, name or src))
+for name, how in (("matcher_kernel_coverage.txt", "scripts/kernel_coverage.py --matchers on the kernel trace of tests/test_gpu_matcher_matrix.py tests/test_gpu_sgm.py tests/test_gpu_bm.py"),
+                  ("suite_kernel_coverage.txt", "scripts/kernel_coverage.py on the kernel trace of the whole -m gpu suite (bench tests excluded)")):
+    if "%s_%s" % (tag, name) in published:
+        published["%s_%s" % (tag, name)] = how                  # a listing derived from a trace: what made it
 sq = "".join(open(f).read() for f in (os.path.join(g, "%s_sq1.txt" % tag), os.path.join(g, "%s_sq2.txt" % tag)) if os.path.exists(f))
 if sq:
     open(os.path.join(p, "%s_pmc_SQ.txt" % tag), "w").write(sq)

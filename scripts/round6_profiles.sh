@@ -70,7 +70,13 @@ for v in 0 1; do echo "JN_STAGE_A_PRIORITY=$v $(JN_STAGE_A_PRIORITY=$v python3 b
 for v in 1 0 1 0; do echo "JN_PACE=$v, the driver's command (--gpus 1 --steps 20 --warmup 5): $(JN_PACE=$v python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-latency-config 2>/dev/null | grep '^{"metric"' | python3 -c 'import sys,json; j=json.loads(sys.stdin.read()); print(j["value"], "pairs/s", j["ms_per_step"], "ms/step")')"; done > $out/${tag}_pace_ab.txt
 for v in 1 0; do echo "JN_PACE=$v, default 200 steps per region: $(JN_PACE=$v python3 bench.py --no-cpu-baseline --no-latency-config 2>/dev/null | grep '^{"metric"' | python3 -c 'import sys,json; j=json.loads(sys.stdin.read()); print(j["value"], "pairs/s", j["ms_per_step"], "ms/step")')"; done >> $out/${tag}_pace_ab.txt
 timeout 1200 python3 scripts/parity_sweep.py 12 2>&1 | grep -v "Opened result\|amdgpu.ids" > $out/${tag}_parity_sweep.txt
-timeout 400 python3 scripts/sgm_stress.py 120 2>&1 | grep -v amdgpu.ids > $out/${tag}_sgm_stress.txt
+{ for m in sgm bm-sad bm-ssd; do timeout 600 python3 scripts/sgm_stress.py --mode $m --configs 300 2>&1 | grep -v amdgpu.ids; done; } > $out/${tag}_sgm_stress.txt
+# which instantiations of the matchers' kernels the matrix (tests/matcher_cases.py) and the two modes' tests launch, then the whole GPU suite: kernel trace only,
+# one pytest process (the bench tests start children of their own)
+fresh ${tag}_cov_matcher; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/${tag}_cov_matcher -- python3 -m pytest tests/test_gpu_matcher_matrix.py tests/test_gpu_sgm.py tests/test_gpu_bm.py -q -m gpu -k "not bench" > $out/${tag}_cov_matcher.log 2>&1
+python3 scripts/kernel_coverage.py $out/${tag}_cov_matcher --matchers > $out/${tag}_matcher_kernel_coverage.txt
+fresh ${tag}_cov_suite; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/${tag}_cov_suite -- python3 -m pytest tests -q -m gpu -k "not bench" > $out/${tag}_cov_suite.log 2>&1
+python3 scripts/kernel_coverage.py $out/${tag}_cov_suite > $out/${tag}_suite_kernel_coverage.txt
 cat $out/${tag}_bm_ssd_summary.txt $out/${tag}_bm_ssd_pmc_mfma.txt | head -30; tail -8 $out/${tag}_collect.log | cut -c1-300; cat $out/${tag}_sgm_summary.txt $out/${tag}_sgm_strips_ab.txt $out/${tag}_merge_in_worker.txt $out/${tag}_node_rate.txt; tail -2 $out/${tag}_parity_sweep.txt
 # ---- round 6: FETCH_SIZE against known bytes, the non-volatile k_delaunay build, a slot's life in the pipeline, 1920x1080 on both routes ----
 bash scripts/probes/fetch_size_probe.sh > $out/${tag}_fetch_size_probe.txt 2>&1

@@ -8,42 +8,17 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import jackal_navigation_amd as jn                       # noqa: E402
 from jackal_navigation_amd import _lib                    # noqa: E402
 from jackal_navigation_amd.device import DeviceArray     # noqa: E402
 from oracle.binding import Oracle, SgmOracle             # noqa: E402
+from matcher_cases import cost_volume, volume_order      # noqa: E402  (the indexing the stage-wise GPU test uses)
 
 
 def d2h(ptr, shape, dtype):
     out = np.empty(shape, dtype)
     _lib.check(_lib.load().jn_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), ptr, out.nbytes), "d2h")
-    return out
-
-
-def cost_volume(gL, gR, D):
-    H, W = gL.shape
-    Cv = np.zeros((H, W, D), np.int32)
-    xs = np.arange(W)
-    for d in range(D):
-        for i in (-1, 0, 1):
-            xl = np.clip(xs + i, 0, W - 1); xr = np.clip(xs + i - d, 0, W - 1)
-            Cv[:, :, d] += np.abs(gL[:, xl].astype(np.int32) - gR[:, xr].astype(np.int32))
-    return Cv
-
-
-def volume_order(D, wide):
-    """d of every stored element of a pixel (sgm_sweep.hip VOLUME LAYOUT / REGISTER LAYOUT)."""
-    NR, DPL = D // 8, D // 4
-    out = np.zeros(D, np.int64)
-    for e in range(D):
-        if wide:
-            c, q, w = e // 32, (e % 32) // 8, e % 8
-            r, half = 4 * c + w // 2, w % 2
-        else:
-            c, q, b = e // 64, (e % 64) // 16, e % 16
-            r, half = 8 * c + 2 * (b // 4) + ((b % 4) >> 1), b & 1
-        out[e] = DPL * q + r + half * NR
     return out
 
 

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
-"""Random-configuration stress of the SGM sweep kernels against the scalar definition (GPU box):  python3 scripts/sgm_stress.py [seconds]
-Sizes from 8x8 to ~700x300 (narrower than the disparity range, single-block and many-block frames), D in {64,128,256}, random
-penalties incl. the 16-bit volume mode (3 P2 > 255), caps, L/R tolerances, sub-pixel on/off, batches of 1-3, both implementations."""
+"""Random-configuration stress of the matchers against their scalar definitions (GPU box):
+    python3 scripts/sgm_stress.py [--mode sgm|bm-sad|bm-ssd] [--configs N | --seconds S]        (SEED=7 in the environment: another walk)
+--configs N (default 300): the seed alone decides the N configurations, on every box.  --seconds S: as many as fit (ad-hoc use).
+Sizes from 8x8 to ~700x300 (narrower than the disparity range, single-block and many-block frames), random caps, L/R tolerances, sub-pixel
+on/off, batches of 1-3 on a handle made for more, padded rows.  sgm: D in {64,128,256}, random penalties, every THIRD configuration in the 16-bit
+volume form (3 P2 > 255).  bm-sad: D any multiple of 8, bm-ssd: of 32; block radius 2-4.  (The fixed edge cases live in tests/matcher_cases.py.)"""
+import argparse
 import os
 import sys
 import time
@@ -11,26 +15,39 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import jackal_navigation_amd as jn                       # noqa: E402
-from jackal_navigation_amd.device import DeviceArray     # noqa: E402
-from oracle.binding import Oracle, SgmOracle             # noqa: E402
+from oracle.binding import Oracle, SgmOracle, BmOracle   # noqa: E402
 from scenes import make_scene, KINDS                     # noqa: E402
+from matcher_run import run                              # noqa: E402
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
+ap = argparse.ArgumentParser()
+ap.add_argument("--mode", choices=["sgm", "bm-sad", "bm-ssd"], default="sgm")
+ap.add_argument("--configs", type=int, default=300)
+ap.add_argument("--seconds", type=float, default=None)
+args = ap.parse_args()
 rng = np.random.default_rng(int(os.environ.get("SEED", "7")))
-o, so = Oracle(), SgmOracle()
+o, so, bo = Oracle(), SgmOracle(), BmOracle()
 t0 = time.time()
-n_cfg = n_pairs = 0
+n_cfg = n_pairs = n_wide = 0
 fixed = [(8, 8), (9, 8), (16, 8), (17, 9), (8, 64), (130, 50), (47, 33), (48, 16), (49, 200), (257, 19)]
-while time.time() - t0 < budget:
+while (time.time() - t0 < args.seconds) if args.seconds is not None else (n_cfg < args.configs):
+    W, H = int(rng.integers(8, 700)), int(rng.integers(8, 300))
     if n_cfg < len(fixed):
         W, H = fixed[n_cfg]
-    else:
-        W, H = int(rng.integers(8, 700)), int(rng.integers(8, 300))
-    D = int(rng.choice([64, 128, 256]))
     cap = int(rng.integers(1, 32))
-    P2 = int(rng.integers(1, 255 - 6 * cap + 1))
-    P1 = int(rng.integers(0, P2 + 1))
-    kw = dict(P1=P1, P2=P2, prefilter_cap=cap, lr_max_diff=int(rng.integers(-1, 4)), subpixel=int(rng.integers(0, 2)))
+    kw = dict(prefilter_cap=cap, lr_max_diff=int(rng.integers(-1, 4)), subpixel=int(rng.integers(0, 2)))
+    if args.mode == "sgm":
+        D = int(rng.choice([64, 128, 256]))
+        lo, hi = (86, 255 - 6 * cap) if n_cfg % 3 == 2 else (1, min(85, 255 - 6 * cap))     # every third configuration: the 16-bit form
+        if lo > hi:
+            cap = kw["prefilter_cap"] = int(rng.integers(1, 29)); hi = 255 - 6 * cap            # 6 cap + 86 <= 255
+        P2 = int(rng.integers(lo, hi + 1))
+        kw.update(P1=int(rng.integers(0, P2 + 1)), P2=P2)
+        n_wide += 3 * P2 > 255
+        Matcher, p, po, definition = jn.Sgm, jn.Sgm.parameters(num_disparities=D, **kw), so.params(D, **kw), so
+    else:
+        D = 32 * int(rng.integers(1, 9)) if args.mode == "bm-ssd" else 8 * int(rng.integers(1, 33))
+        kw.update(block_radius=int(rng.integers(2, 5)), cost_function=1 if args.mode == "bm-ssd" else 0)
+        Matcher, p, po, definition = jn.Bm, jn.Bm.parameters(num_disparities=D, **kw), bo.params(D, **kw), bo
     n = int(rng.integers(1, 4))
     pairs = []
     for b in range(n):
@@ -41,29 +58,19 @@ while time.time() - t0 < budget:
             pairs.append((rng.integers(0, 256, (H, W)).astype(np.uint8), rng.integers(0, 256, (H, W)).astype(np.uint8)))
         else:
             pairs.append(o.synth_pair(W, H, min(D, max(8, W // 4)), int(rng.integers(0, 1 << 30))))
-    Ls = np.stack([p[0] for p in pairs]); Rs = np.stack([p[1] for p in pairs])
-    pitch = W + int(rng.integers(0, 3)) * 8                       # rows of the caller's images may be padded
-    Lp = np.zeros((n, H, pitch), np.uint8); Rp = np.zeros((n, H, pitch), np.uint8)
-    Lp[:, :, :W] = Ls; Rp[:, :, :W] = Rs
-    Lp[:, :, W:] = 199; Rp[:, :, W:] = 7                            # padding bytes must never be read as pixels
-    dL, dR = DeviceArray.from_numpy(Lp), DeviceArray.from_numpy(Rp)
-    dD = DeviceArray((n, H, W), np.int16)
-    with jn.Sgm(jn.Sgm.parameters(num_disparities=D, **kw), W, H, max_batch=n + int(rng.integers(0, 3))) as s:   # handle larger than the batch
-        if n > 1:                                                    # a smaller batch first: the handle's buffers are re-used
-            s.process_batch(n - 1, dL.ptr + H * pitch, dR.ptr + H * pitch, pitch, H * pitch, dD.ptr)
-            first = dD.numpy()[: n - 1].copy()
-        s.process_batch(n, dL.ptr, dR.ptr, pitch, H * pitch, dD.ptr)
-        out = dD.numpy()
-        if n > 1 and not np.array_equal(first, out[1:]):
-            print("MISMATCH between a batch of %d and the same frames inside a batch of %d (%dx%d D=%d %s)" % (n - 1, n, W, H, D, kw)); sys.exit(1)
-    po = so.params(D, **kw)
+    Ls = np.stack([q[0] for q in pairs]); Rs = np.stack([q[1] for q in pairs])
+    pad = int(rng.choice([0, 8, 16, 13]))                        # rows of the caller's images may be padded (and then start at odd addresses)
+    try:        # padding poisoned, the handle larger than the batch, a smaller batch first (the handle's buffers are re-used)
+        out, _, _ = run(jn, Matcher, p, Ls, Rs, pad=pad, gap=int(rng.integers(0, 3)), extra=int(rng.integers(0, 3)), smaller_first=True)
+    except AssertionError as e:
+        print("MISMATCH %s %dx%d D=%d n=%d %s: %s" % (args.mode, W, H, D, n, kw, e)); sys.exit(1)
     for b in range(n):
-        exp = so.process(po, Ls[b], Rs[b])
+        exp = definition.process(po, Ls[b], Rs[b])
         if not np.array_equal(out[b], exp):
             bad = np.argwhere(out[b] != exp)
-            print("MISMATCH %dx%d D=%d n=%d frame %d %s: %d pixels, first %s got %d exp %d" % (W, H, D, n, b, kw, len(bad), bad[0].tolist(), out[b][tuple(bad[0])], exp[tuple(bad[0])]))
+            print("MISMATCH %s %dx%d D=%d n=%d pad=%d frame %d %s: %d pixels, first %s got %d exp %d" % (
+                args.mode, W, H, D, n, pad, b, kw, len(bad), bad[0].tolist(), out[b][tuple(bad[0])], exp[tuple(bad[0])]))
             sys.exit(1)
-    for a in (dL, dR, dD):
-        a.free()
     n_cfg += 1; n_pairs += n
-print("sgm stress PASSED: %d configurations, %d pairs, all bit-identical to oracle/sgm_oracle.cpp (%.0f s)" % (n_cfg, n_pairs, time.time() - t0))
+print("%s stress PASSED: %d configurations%s, %d pairs, all bit-identical to oracle/%s_oracle.cpp (%.0f s)" % (
+    args.mode, n_cfg, " (%d in the 16-bit form)" % n_wide if args.mode == "sgm" else "", n_pairs, "sgm" if args.mode == "sgm" else "bm", time.time() - t0))

@@ -13,19 +13,8 @@ def sgm():
 
 
 def run(jn, p, Ls, Rs):
-    from jackal_navigation_amd.device import DeviceArray
-    n, H, W = Ls.shape
-    dL, dR = DeviceArray.from_numpy(Ls), DeviceArray.from_numpy(Rs)
-    dD = DeviceArray((n, H, W), np.int16)
-    with jn.Sgm(p, W, H, max_batch=n) as s:
-        s.process_batch(n, dL.ptr, dR.ptr, W, H * W, dD.ptr)
-        t = s.last_times()
-        du8 = DeviceArray((n, H, W), np.uint8)
-        s.to_u8(dD.ptr, du8.ptr, n * H * W)
-    out, u8 = dD.numpy(), du8.numpy()
-    for a in (dL, dR, dD, du8):
-        a.free()
-    return out, u8, t
+    from matcher_run import run as run_batch
+    return run_batch(jn, jn.Sgm, p, Ls, Rs)
 
 
 @pytest.mark.parametrize("W,H,D,scene,n,kw", [

@@ -33,13 +33,13 @@ def _cost(gL, gR, x, y, d):
     return sum(abs(int(gL[y, min(max(x + i, 0), W - 1)]) - int(gR[y, min(max(x + i - d, 0), W - 1)])) for i in (-1, 0, 1))
 
 
-@pytest.mark.parametrize("dx,dy", [(1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (-1, 1), (1, -1)])
-def test_path_recurrence_against_a_python_restatement(sgm, dx, dy):
-    rng = np.random.default_rng(3)
-    H, W, D, P1, P2 = 7, 9, 6, 3, 11
-    gL = rng.integers(0, 63, (H, W)).astype(np.uint8); gR = rng.integers(0, 63, (H, W)).astype(np.uint8)
-    got = sgm.path(gL, gR, D, P1, P2, dx, dy)
-    exp = np.zeros((H, W, D), int)
+DIRECTIONS = [(1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (-1, 1), (1, -1)]
+
+
+def _path_literal(gL, gR, D, P1, P2, dx, dy):
+    """include/jn_sgm.h's recurrence in Python integers: nothing is clamped or narrowed anywhere"""
+    H, W = gL.shape
+    exp = np.zeros((H, W, D), np.int64)
     for y0 in range(H):
         for x0 in range(W):
             if 0 <= x0 - dx < W and 0 <= y0 - dy < H:
@@ -56,7 +56,42 @@ def test_path_recurrence_against_a_python_restatement(sgm, dx, dy):
                 exp[y, x] = cur
                 prev = cur
                 x += dx; y += dy
-    assert np.array_equal(got.astype(int), exp)
+    return exp
+
+
+@pytest.mark.parametrize("dx,dy", DIRECTIONS)
+def test_path_recurrence_against_a_python_restatement(sgm, dx, dy):
+    rng = np.random.default_rng(3)
+    H, W, D, P1, P2 = 7, 9, 6, 3, 11
+    gL = rng.integers(0, 63, (H, W)).astype(np.uint8); gR = rng.integers(0, 63, (H, W)).astype(np.uint8)
+    assert np.array_equal(sgm.path(gL, gR, D, P1, P2, dx, dy).astype(int), _path_literal(gL, gR, D, P1, P2, dx, dy))
+
+
+@pytest.mark.parametrize("P1,P2,cap,H,W", [
+    (7, 69, 31, 7, 9),         # 6 cap + P2 = 255 with the largest cap
+    (125, 249, 1, 3, 150),     # the largest P2 (cap = 1): a path needs ~100 steps to climb to the limit
+    (249, 249, 1, 3, 150),     # ... with P1 = P2
+    (10, 85, 20, 7, 9),        # 3 P2 = 255: the largest P2 of the kernels' byte form
+    (10, 86, 20, 7, 9),        # 3 P2 = 258: their 16-bit form
+    (0, 64, 31, 7, 9),         # P1 = 0
+])
+def test_path_recurrence_at_the_parameter_limits(sgm, P1, P2, cap, H, W):
+    """The parameter sets the GPU is judged at (tests/matcher_cases.py), on prefiltered images that sit at 0 and 2 cap with one disparity that
+    matches: the oracle's bytes equal the unclamped restatement, which itself stays within 6 cap + P2 <= 255 and reaches it; where 3 P2 > 255
+    the three-path sums of L_r - C really leave a byte."""
+    rng = np.random.default_rng(P2)
+    D = 6
+    t = (rng.integers(0, 2, (H, W + 2)) * 2 * cap).astype(np.uint8)
+    gL, gR = t[:, :W].copy(), t[:, 2:].copy()                              # true disparity 2
+    lit = {dxy: _path_literal(gL, gR, D, P1, P2, *dxy) for dxy in DIRECTIONS}
+    for dxy in DIRECTIONS:
+        assert np.array_equal(sgm.path(gL, gR, D, P1, P2, *dxy).astype(np.int64), lit[dxy]), dxy
+    assert max(int(v.max()) for v in lit.values()) == 6 * cap + P2 <= 255
+    C = np.array([[[_cost(gL, gR, x, y, d) for d in range(D)] for x in range(W)] for y in range(H)], np.int64)
+    if H >= 7:                                                             # (the long thin frames have no vertical path to speak of)
+        down = sum(lit[dxy] - C for dxy in ((0, 1), (1, 1), (-1, 1)))
+        assert down.min() == 0 and (down.max() == 3 * P2 if P1 else down.max() > 2 * P2)
+        assert (down.max() > 255) == (3 * P2 > 255)
 
 
 def test_whole_mode_on_a_tiny_case_by_hand(sgm):
