@@ -10,3 +10,5 @@ from .elas import Elas  # noqa: F401
 from . import node, device, parallel, navigate  # noqa: F401
 from .sgm import Sgm, SGM_EXPORTS  # noqa: F401
 from .bm import Bm, BM_EXPORTS  # noqa: F401
+from . import costmap  # noqa: F401
+from .costmap import CostmapParams, COSTMAP_EXPORTS  # noqa: F401

@@ -232,6 +232,32 @@ jn_status jn_scan_allreduce(jn_comm* c, int32_t n, int32_t bins, double* dBins, 
   return JN_OK;
 }
 
+// The obstacle costmap's merge (include/jn_costmap.h): MAX of the hit counts over the rigs, through the SAME collective as the scan's —
+// counts negated into the packed buffer, one MIN all-reduce, unpacked (+inf, a failed rank's identity, gives 0), the grid recomputed
+// from the merged counts and the bins given.  Under c->m and on the communicator's stream like every other collective of it.
+jn_status jn_costmap_allreduce(jn_comm* c, const jn_scan_params* sp, const jn_costmap_params* cp, int32_t n, const double* dBins,
+                               uint16_t* dHits, int8_t* dGrid) {
+  if (!c || !sp || !costmap_params_valid(cp) || n < 1 || !dHits || !dGrid || sp->bins < 1 || sp->bins > 1024) return JN_ERR_INVALID;
+  if (c->dead.load()) return JN_ERR_COMM;
+  Rccl* R = rccl();
+  if (!R) return JN_ERR_COMM;
+  const size_t count = (size_t)n * cp->cells_x * cp->cells_y;
+  {
+    std::lock_guard<std::mutex> guard(c->m);
+    if (c->dead.load()) return JN_ERR_COMM;
+    HIP_TRY_C(hipSetDevice(c->device));
+    if (const jn_status gs = grow_flat(c, count); gs != JN_OK) return gs;
+    launch_costmap_pack(c->stream, (long long)count, dHits, c->flat, true);
+    RCCL_TRY(R, R->AllReduce(c->flat, c->flat, count, ncclDouble, ncclMin, c->comm, c->stream));
+    launch_costmap_pack(c->stream, (long long)count, dHits, c->flat, false);
+    launch_costmap_finish(c->stream, *sp, *cp, n, nullptr, dHits, dBins, dGrid);
+  }
+  const jn_status ws = bounded_stream_wait(c);
+  if (ws != JN_OK) return ws;
+  HIP_TRY_C(hipGetLastError());
+  return JN_OK;
+}
+
 extern "C++" {
 namespace jnav {
 // The batch pipeline's form (jn_elas_set_comm): nothing waits on the host; the slot's stream continues behind `done`.

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "jn_types.h"
 #include "../../include/jn_stereo.h"
+#include "../../include/jn_costmap.h"
 
 namespace jnav {
 
@@ -127,5 +128,18 @@ void launch_remap(hipStream_t st, int n, const uint8_t* src, int sw, int sh, int
 // Point cloud (-g): counts per column, exclusive scan, scatter.  col_count: [W+1] int64 scratch.
 void launch_point_cloud(hipStream_t st, const jn_scan_params& sp, const uint8_t* disp, int W, int H, float* xyz,
                         long long* col_count);
+
+// Obstacle costmap (include/jn_costmap.h; costmap.hip) ------------------------------------------------
+bool costmap_params_valid(const jn_costmap_params* cp);
+size_t costmap_scratch_bytes(const jn_costmap_params& cp, int n);     // acc: one u32 per cell and frame
+// Clear of acc, accumulate, finish, all on `st`: disp [n][H][W] u8 (+ lut unless cp.from_cloud) -> hits / grid [n][cells_y][cells_x];
+// bins [n][sp.bins] may be null (no free cells).  The only error is the clear's.
+hipError_t launch_costmap(hipStream_t st, const jn_scan_params& sp, const jn_costmap_params& cp, int n, const uint8_t* disp, const uint8_t* lut,
+                          int W, int H, const double* bins, uint32_t* acc, uint16_t* hits, int8_t* grid);
+// The finish alone.  acc == nullptr: grid recomputed from the hits given (after a cross-rig merge).
+void launch_costmap_finish(hipStream_t st, const jn_scan_params& sp, const jn_costmap_params& cp, int n, const uint32_t* acc, uint16_t* hits,
+                           const double* bins, int8_t* grid);
+// Cross-rig merge: hits -> negated doubles in `flat` [count], or back (+inf -> 0).
+void launch_costmap_pack(hipStream_t st, long long count, uint16_t* hits, double* flat, bool pack);
 
 }  // namespace jnav

@@ -12,8 +12,9 @@
 #include <cstdlib>
 #include <cstring>
 #include "../../include/jn_sgm.h"
+#include "../../include/jn_costmap.h"
 #include "sgm_sweep.h"
-#include "kernels.h"            // launch_scan: the node's tail on a slot's stream (jn_sgm_submit_scan)
+#include "kernels.h"            // launch_scan, launch_costmap: the node's tail on a slot's stream (jn_sgm_submit_scan)
 
 namespace {
 
@@ -46,6 +47,9 @@ struct jn_sgm {
   Extra extra[kSgmSlots - 1];
   unsigned long long* scan_scratch[kSgmSlots] = {};   // [max_batch][4] per slot, the scan tail's extrema
   bool pending[kSgmSlots] = {};
+  // the obstacle costmap as part of a slot's scan tail (jn_sgm_attach_costmap, include/jn_costmap.h): acc [max_batch][cells] u32, allocated by the attach call
+  struct Costmap { bool on = false; jn_costmap_params cp = {}; uint16_t* hits = nullptr; int8_t* grid = nullptr; uint32_t* acc = nullptr; size_t acc_bytes = 0; };
+  Costmap costmap[kSgmSlots];
   static_assert(kSgmSlots == sizeof(ev_end) / sizeof(ev_end[0]), "one end event per slot");
 };
 
@@ -76,6 +80,7 @@ void jn_sgm_destroy(jn_sgm* h) {
     if (x.stream && !x.shared) hipStreamDestroy(x.stream);
   }
   for (auto& q : h->scan_scratch) hipFree(q);
+  for (auto& c : h->costmap) hipFree(c.acc);
   jnav_sgm::sweep_release(h->sb);
   hipFree(h->sb.gm); hipFree(h->sb.volF); hipFree(h->sb.volH0); hipFree(h->sb.volH1); hipFree(h->sb.gx); hipFree(h->sb.flags); hipFree(h->sb.minr); hipFree(h->sb.dl);
   for (auto& e : h->ev) if (e) hipEventDestroy(e);
@@ -193,11 +198,32 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
     hipLaunchKernelGGL(k_sgm_to_u8, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, dDisp, h->p.subpixel ? 1 : 0, dDispU8, px);
     jnav::launch_scan(st, *sp, n, nullptr, dDispU8, dLut, h->W, h->H, dBins, dMeta, h->scan_scratch[slot]);
   }
+  if (sp && h->costmap[slot].on) {                              // the obstacle costmap of the map and the bins the tail has just written, same stream
+    const jn_sgm::Costmap& c = h->costmap[slot];
+    SGM_TRY(jnav::launch_costmap(st, *sp, c.cp, n, dDispU8, dLut, h->W, h->H, dBins, c.acc, c.hits, c.grid));
+  }
   // the batch's end: behind the scan tail, not behind the sweeps (ev[3] stays the end of the winner-takes-all timing)
   if (!h->ev_end[slot]) SGM_TRY(hipEventCreateWithFlags(&h->ev_end[slot], hipEventDisableTiming));
   SGM_TRY(hipEventRecord(h->ev_end[slot], st));
   SGM_TRY(hipGetLastError());
   h->pending[slot] = true;
+  return JN_OK;
+}
+
+jn_status jn_sgm_attach_costmap(jn_sgm* h, int32_t slot, const jn_costmap_params* cp, uint16_t* dHits, int8_t* dGrid) {
+  if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
+  if (cp && (!jnav::costmap_params_valid(cp) || !dHits || !dGrid)) return JN_ERR_INVALID;
+  if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
+  jn_sgm::Costmap& c = h->costmap[slot];
+  if (!cp) { c.on = false; c.hits = nullptr; c.grid = nullptr; return JN_OK; }
+  const size_t need = jnav::costmap_scratch_bytes(*cp, h->max_batch);
+  if (need > c.acc_bytes) {                                     // grow-only; the slot is idle, nothing reads the old grid
+    SGM_TRY(hipSetDevice(h->device));
+    if (c.acc) { hipFree(c.acc); c.acc = nullptr; c.acc_bytes = 0; }
+    SGM_TRY(hipMalloc(reinterpret_cast<void**>(&c.acc), need));
+    c.acc_bytes = need;
+  }
+  c.on = true; c.cp = *cp; c.hits = dHits; c.grid = dGrid;
   return JN_OK;
 }
 

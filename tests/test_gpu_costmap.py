@@ -1,0 +1,407 @@
+"""The obstacle costmap (include/jn_costmap.h) on the GPU against its scalar definition (tests/costmap_def.py): hits and the occupied
+cells bit-identical, the free / unknown split equal away from bin edges; the attached form on the ELAS and SGM slots; the cross-rig merge."""
+import ctypes as C
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+
+import costmap_def as cd
+from scenes import make_scene
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def run_costmap(sp, cp, maps, lut, with_bins=True):
+    """maps [n][H][W] u8 (numpy) -> (hits, grid, bins) from jn_obstacle_costmap, the bins from the scan of the same maps with the same rule."""
+    from jackal_navigation_amd import costmap, node
+    from jackal_navigation_amd.device import DeviceArray
+    n, H, W = maps.shape
+    dD = DeviceArray.from_numpy(maps)
+    bins = DeviceArray((n, sp.bins), np.float64); meta = DeviceArray((n, 4), np.float64)
+    if cp.from_cloud:
+        node.obstacle_scan_cloud(sp, n, dD.ptr, W, H, bins.ptr, meta.ptr)
+    else:
+        node.obstacle_scan(sp, n, dD.ptr, lut.ptr, W, H, bins.ptr, meta.ptr)
+    hits = DeviceArray.from_numpy(np.full((n, cp.cells_y, cp.cells_x), 0xABCD, np.uint16))
+    grid = DeviceArray.from_numpy(np.full((n, cp.cells_y, cp.cells_x), 77, np.int8))
+    costmap.obstacle_costmap(sp, cp, n, dD.ptr, None if cp.from_cloud else lut.ptr, W, H, bins.ptr if with_bins else None, hits.ptr, grid.ptr)
+    return hits.numpy(), grid.numpy(), bins.numpy()
+
+
+def check_against_definition(sp, cp, maps, lut_np, hits, grid, bins, what):
+    for f in range(maps.shape[0]):
+        want = cd.hits(sp, cp, maps[f], lut_np)
+        assert np.array_equal(hits[f], want), (what, f, int((hits[f] != want).sum()))
+        g, decided = cd.classify(sp, cp, want, None if bins is None else bins[f])
+        assert np.array_equal(grid[f] == 100, g == 100), (what, f)
+        assert set(np.unique(grid[f])) <= {-1, 0, 100}, (what, f)
+        assert np.array_equal(grid[f][decided], g[decided]), (what, f, int((grid[f][decided] != g[decided]).sum()))
+        if bins is None:
+            assert not (grid[f] == 0).any(), (what, f)
+
+
+def random_maps(rng, n, H, W):
+    """Every disparity value occurs, 0 / 1 / 2 / 255 and 7 (w = 0 under tweak_w0) often; columns of constant disparity (the runs the
+    kernel keeps in registers) next to pixel noise (a run of one)."""
+    m = rng.integers(0, 256, (n, H, W)).astype(np.uint8)
+    special = rng.random((n, H, W))
+    for v, lo in ((0, 0.00), (1, 0.05), (2, 0.10), (255, 0.15), (7, 0.20)):
+        m[(special >= lo) & (special < lo + 0.05)] = v
+    for f in range(n):
+        for _ in range(12):
+            x0, x1 = sorted(rng.integers(0, W, 2)); y0, y1 = sorted(rng.integers(0, H, 2))
+            m[f, y0:y1 + 1, x0:x1 + 1] = rng.integers(3, 120)
+    return m
+
+
+def tweak_w0(sp):
+    """Disparity 7 gets homogeneous w = Q[14] * 7 + Q[15] = 0 exactly (the other terms of that row are 0)."""
+    sp.Q[15] = -(sp.Q[14] * 7.0)
+    return sp
+
+
+GRIDS = {
+    "default": {},
+    "1x1": dict(cells_x=1, cells_y=1, resolution=2.0, origin_x=0.5, origin_y=-1.0, min_hits=1),
+    "7x13": dict(cells_x=7, cells_y=13, resolution=0.31, origin_x=0.2, origin_y=-2.0, min_hits=2),
+    "512x512": dict(cells_x=512, cells_y=512, resolution=0.02, origin_x=0.0, origin_y=-5.12, min_hits=1),
+    "mostly_outside": dict(cells_x=40, cells_y=30, resolution=0.05, origin_x=3.0, origin_y=1.0, min_hits=1),
+    "behind": dict(cells_x=16, cells_y=16, resolution=0.25, origin_x=-6.0, origin_y=-2.0, min_hits=1),
+}
+
+
+@pytest.mark.parametrize("from_cloud", [0, 1])
+@pytest.mark.parametrize("grid_name", sorted(GRIDS))
+def test_random_maps_equal_the_definition(jn, from_cloud, grid_name):
+    from jackal_navigation_amd import costmap, node
+    W, H, n = 200, 37, 3                                      # neither a multiple of the kernel's 256 columns nor of its 16 rows
+    rng = np.random.default_rng(11 + from_cloud)
+    sp = tweak_w0(node.scan_params(W, H))
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cp = costmap.costmap_params(from_cloud=from_cloud, **GRIDS[grid_name])
+    maps = random_maps(rng, n, H, W)
+    assert not np.array_equal(maps[0], maps[1])
+    hits, grid, bins = run_costmap(sp, cp, maps, lut)
+    check_against_definition(sp, cp, maps, lut.numpy(), hits, grid, bins, grid_name)
+    if grid_name in ("default", "512x512", "7x13"):
+        assert hits.sum() > 0 and (grid == 100).any()
+    # n = 1 gives frame 0 of the batch
+    h1, g1, _ = run_costmap(sp, cp, maps[:1], lut)
+    assert np.array_equal(h1[0], hits[0]) and np.array_equal(g1[0], grid[0])
+    # without bins no cell is free and the rest does not change
+    h2, g2, _ = run_costmap(sp, cp, maps, lut, with_bins=False)
+    assert np.array_equal(h2, hits) and not (g2 == 0).any() and np.array_equal(g2 == 100, grid == 100)
+
+
+@pytest.mark.parametrize("from_cloud", [0, 1])
+def test_free_cells_in_front_of_a_far_wall(jn, from_cloud):
+    """A wall a few metres away (one small disparity everywhere; a nearer post in the second frame): the cells between the robot and the
+    wall are free, those behind it and outside the fan unknown, and all three values equal the definition's."""
+    from jackal_navigation_amd import costmap, node
+    W, H = 320, 180
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cp = costmap.costmap_params(from_cloud=from_cloud)
+    maps = np.full((2, H, W), 5, np.uint8)
+    maps[1, :, 100:130] = 14
+    hits, grid, bins = run_costmap(sp, cp, maps, lut)
+    check_against_definition(sp, cp, maps, lut.numpy(), hits, grid, bins, "wall")
+    for f in range(2):
+        assert (grid[f] == 0).sum() > 500 and (grid[f] == -1).sum() > 500 and (grid[f] == 100).any(), f
+    assert (grid[0] == 0).sum() > (grid[1] == 0).sum()        # the post shadows the cells behind it
+
+
+def test_counts_saturate_at_65535(jn):
+    """One 100 m cell collects a whole 640x480 frame of obstacle pixels: 307200 of them, stored as 65535."""
+    from jackal_navigation_amd import costmap, node
+    W, H = 640, 480
+    sp = node.scan_params(W, H)
+    sp.gp_height_thresh = -1e9                                # no point is ground
+    cp = costmap.costmap_params(from_cloud=1, cells_x=1, cells_y=1, resolution=100.0, origin_x=-50.0, origin_y=-50.0, min_hits=1)
+    maps = np.full((2, H, W), 40, np.uint8)
+    maps[1, :100] = 0                                         # 243200 obstacle pixels in the second frame
+    maps[1, 100:, 150:] = 0                                   # ... 57000: below the limit
+    assert cd.obstacle_cells(sp, cp, maps[0], None).size == W * H
+    hits, grid, bins = run_costmap(sp, cp, maps, None)
+    assert hits[0, 0, 0] == 65535 and hits[1, 0, 0] == 380 * 150 and grid[0, 0, 0] == 100
+    check_against_definition(sp, cp, maps, None, hits, grid, bins, "saturation")
+
+
+@pytest.mark.parametrize("W,H,kind", [(640, 480, "strips"), (640, 480, "blobs"), (320, 180, "slanted"), (320, 180, "grain")])
+def test_elas_scenes_equal_the_definition(jn, W, H, kind):
+    """Synthetic scenes through ELAS and the node's tail: the costmap of the u8 map the GPU produced, both rules."""
+    from jackal_navigation_amd import costmap, node
+    from jackal_navigation_amd.device import DeviceArray
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    pairs = [make_scene(kind, W, H, 60, 5 + t) for t in range(2)]
+    dL = DeviceArray.from_numpy(np.stack([p[0] for p in pairs])); dR = DeviceArray.from_numpy(np.stack([p[1] for p in pairs]))
+    d1 = DeviceArray((2, H, W), np.float32); d2 = DeviceArray((2, H, W), np.float32); u8 = DeviceArray((2, H, W), np.uint8)
+    bins = DeviceArray((2, sp.bins), np.float64); meta = DeviceArray((2, 4), np.float64)
+    with jn.Elas(jn.Elas.parameters(0), W, H, max_batch=2) as e:
+        e.process_batch(2, dL.ptr, dR.ptr, W, W * H, d1.ptr, d2.ptr)
+    node.disparity_scan(sp, 2, d1.ptr, lut.ptr, W, H, u8.ptr, bins.ptr, meta.ptr)
+    maps = u8.numpy()
+    assert (maps > 2).mean() > 0.2
+    for fc in (0, 1):
+        cp = costmap.costmap_params(from_cloud=fc)
+        hits, grid, b = run_costmap(sp, cp, maps, lut)
+        if not fc:
+            assert np.array_equal(b, bins.numpy())
+        check_against_definition(sp, cp, maps, lut.numpy(), hits, grid, b, (kind, fc))
+        assert hits.sum() > 0
+
+
+def test_the_binned_points_are_the_point_clouds(jn):
+    """costmap.hip restates kernels.hip's reprojection.  With the -g rule, the ground test switched off and min_hits = 1 the occupied cells
+    must be the cells of jn_point_cloud's points (float32, so a point within float32 rounding of a cell edge may sit on either side)."""
+    from jackal_navigation_amd import costmap, node
+    from jackal_navigation_amd.device import DeviceArray
+    W, H = 320, 180
+    rng = np.random.default_rng(3)
+    sp = node.scan_params(W, H)
+    sp.gp_height_thresh = -1e9
+    cp = costmap.costmap_params(from_cloud=1, min_hits=1, cells_x=200, cells_y=200, resolution=0.05, origin_x=0.0, origin_y=-5.0)
+    m = random_maps(rng, 1, H, W)
+    hits, grid, _ = run_costmap(sp, cp, m, None)
+    dM = DeviceArray.from_numpy(m[0])
+    pts = node.point_cloud(sp, dM.ptr, W, H).astype(np.float64)
+    assert pts.shape[0] == int((m[0] >= 2).sum())
+    sx, sy = (pts[:, 0] - cp.origin_x) / cp.resolution, (pts[:, 1] - cp.origin_y) / cp.resolution
+    tol = (np.abs(pts[:, :2]).max(axis=1) * 2.0 ** -22 + 1e-12) / cp.resolution        # float32 rounding of a coordinate, in cells
+    sure, maybe = set(), set()
+    for ddx in (-1, 0, 1):
+        for ddy in (-1, 0, 1):
+            fx, fy = np.floor(sx + ddx * tol), np.floor(sy + ddy * tol)
+            ok = (fx >= 0) & (fx < cp.cells_x) & (fy >= 0) & (fy < cp.cells_y)
+            maybe |= set((fy[ok].astype(np.int64) * cp.cells_x + fx[ok].astype(np.int64)).tolist())
+    fx0, fy0 = np.floor(sx), np.floor(sy)
+    stable = (np.floor(sx - tol) == fx0) & (np.floor(sx + tol) == fx0) & (np.floor(sy - tol) == fy0) & (np.floor(sy + tol) == fy0)
+    inside = stable & (fx0 >= 0) & (fx0 < cp.cells_x) & (fy0 >= 0) & (fy0 < cp.cells_y)
+    sure = set((fy0[inside].astype(np.int64) * cp.cells_x + fx0[inside].astype(np.int64)).tolist())
+    occ = set(np.flatnonzero(grid[0].reshape(-1) == 100).tolist())
+    assert len(sure) > 500
+    assert sure <= occ <= maybe, (len(sure - occ), len(occ - maybe))
+    # and the counts: every stable point is counted in its cell
+    want = np.bincount(fy0[inside].astype(np.int64) * cp.cells_x + fx0[inside].astype(np.int64), minlength=cp.cells_x * cp.cells_y)
+    assert (hits[0].reshape(-1).astype(np.int64) >= np.minimum(want, 65535)).all()
+    assert abs(int(hits[0].sum()) - int(want.sum())) <= int((~stable).sum())
+
+
+def _standalone(sp, cp, n, u8, lut, bins, W, H):
+    from jackal_navigation_amd import costmap
+    from jackal_navigation_amd.device import DeviceArray
+    hits = DeviceArray((n, cp.cells_y, cp.cells_x), np.uint16); grid = DeviceArray((n, cp.cells_y, cp.cells_x), np.int8)
+    costmap.obstacle_costmap(sp, cp, n, u8.ptr, lut.ptr, W, H, bins.ptr, hits.ptr, grid.ptr)
+    return hits.numpy(), grid.numpy()
+
+
+def test_attached_to_elas_slots(jn):
+    """Two slots in flight with different grids attached: each slot's grid equals the standalone call on that slot's dDispU8 / dBins; the
+    scan outputs are those of a handle with nothing attached; after detaching the output buffers are no longer written."""
+    from jackal_navigation_amd import costmap, node
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, B, S = 320, 180, 2, 2
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cps = [costmap.costmap_params(), costmap.costmap_params(cells_x=64, cells_y=96, resolution=0.1, origin_y=-4.8, min_hits=1, from_cloud=1)]
+    pairs = [[node.synth_pair(W, H, 30 + 9 * s, 40 + 10 * s + t) for t in range(B)] for s in range(S)]
+    dL = [DeviceArray.from_numpy(np.stack([p[0] for p in ps])) for ps in pairs]
+    dR = [DeviceArray.from_numpy(np.stack([p[1] for p in ps])) for ps in pairs]
+
+    def buffers():
+        return [dict(d1=DeviceArray.from_numpy(np.zeros((B, H, W), np.float32)), d2=DeviceArray.from_numpy(np.zeros((B, H, W), np.float32)),
+                     u8=DeviceArray((B, H, W), np.uint8), bins=DeviceArray((B, sp.bins), np.float64), meta=DeviceArray((B, 4), np.float64),
+                     st=(C.c_int32 * B)()) for _ in range(S)]
+
+    def submit_all(e, bufs):
+        for s in range(S):
+            b = bufs[s]
+            e.submit_scan(s, B, dL[s].ptr, dR[s].ptr, W, H * W, b["d1"].ptr, b["d2"].ptr, sp, lut.ptr, b["u8"].ptr, b["bins"].ptr, b["meta"].ptr, b["st"])
+        for s in range(S):
+            e.wait(s)
+        return [tuple(bufs[s][k].numpy().copy() for k in ("d1", "d2", "u8", "bins", "meta")) for s in range(S)]
+
+    with jn.Elas(jn.Elas.parameters(0), W, H, max_batch=B, slots=S, host_threads=4) as e:
+        bufs = buffers()
+        plain = submit_all(e, bufs)
+        outs = [(DeviceArray.from_numpy(np.full((B, cp.cells_y, cp.cells_x), 0xABCD, np.uint16)),
+                 DeviceArray.from_numpy(np.full((B, cp.cells_y, cp.cells_x), 77, np.int8))) for cp in cps]
+        for s in range(S):
+            costmap.attach(e, s, cps[s], outs[s][0].ptr, outs[s][1].ptr)
+        with pytest.raises(jn.JnError):
+            costmap.attach(e, S, cps[0], outs[0][0].ptr, outs[0][1].ptr)      # no such slot
+        with pytest.raises(jn.JnError):
+            costmap.attach(e, 0, cps[0], None, outs[0][1].ptr)
+        for rep in range(2):                                                   # twice: the accumulation grid is cleared per batch
+            attached = submit_all(e, bufs)
+            for s in range(S):
+                for a, b in zip(plain[s], attached[s]):
+                    assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (s, rep)
+                h, g = _standalone(sp, cps[s], B, bufs[s]["u8"], lut, bufs[s]["bins"], W, H)
+                assert np.array_equal(outs[s][0].numpy(), h) and np.array_equal(outs[s][1].numpy(), g), (s, rep)
+                assert h.sum() > 0 and (g == 100).any()
+                check_against_definition(sp, cps[s], attached[s][2], lut.numpy(), h, g, attached[s][3], ("elas", s))
+        costmap.attach(e, 0, None)
+        outs[0][0].upload(np.full((B, cps[0].cells_y, cps[0].cells_x), 0x1234, np.uint16)); outs[0][1].upload(np.full((B, cps[0].cells_y, cps[0].cells_x), 55, np.int8))
+        outs[1][0].upload(np.zeros((B, cps[1].cells_y, cps[1].cells_x), np.uint16))
+        submit_all(e, bufs)
+        assert (outs[0][0].numpy() == 0x1234).all() and (outs[0][1].numpy() == 55).all()      # detached: untouched
+        assert outs[1][0].numpy().sum() > 0                                                     # slot 1 still attached
+        costmap.attach(e, 1, None)
+
+
+@pytest.mark.parametrize("subpixel", [0, 1])
+def test_attached_to_sgm_slots(jn, subpixel):
+    from jackal_navigation_amd import costmap, node
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, B, S = 320, 180, 2, 2
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cps = [costmap.costmap_params(min_hits=2), costmap.costmap_params(cells_x=50, cells_y=33, resolution=0.2, origin_y=-3.3, min_hits=1)]
+    pairs = [[node.synth_pair(W, H, 28 + 11 * s, 90 + 10 * s + t) for t in range(B)] for s in range(S)]
+    dL = [DeviceArray.from_numpy(np.stack([p[0] for p in ps])) for ps in pairs]
+    dR = [DeviceArray.from_numpy(np.stack([p[1] for p in ps])) for ps in pairs]
+    bufs = [dict(dd=DeviceArray((B, H, W), np.int16), u8=DeviceArray((B, H, W), np.uint8), bins=DeviceArray((B, sp.bins), np.float64),
+                 meta=DeviceArray((B, 4), np.float64)) for _ in range(S)]
+
+    def submit_all(m):
+        for s in range(S):
+            b = bufs[s]
+            m.submit_scan(s, B, dL[s].ptr, dR[s].ptr, W, H * W, b["dd"].ptr, sp, lut.ptr, b["u8"].ptr, b["bins"].ptr, b["meta"].ptr)
+        for s in range(S):
+            m.wait(s)
+        return [tuple(bufs[s][k].numpy().copy() for k in ("dd", "u8", "bins", "meta")) for s in range(S)]
+
+    with jn.Sgm(jn.Sgm.parameters(num_disparities=64, subpixel=subpixel), W, H, max_batch=B) as m:
+        plain = submit_all(m)
+        outs = [(DeviceArray.from_numpy(np.full((B, cp.cells_y, cp.cells_x), 0xABCD, np.uint16)),
+                 DeviceArray.from_numpy(np.full((B, cp.cells_y, cp.cells_x), 77, np.int8))) for cp in cps]
+        for s in range(S):
+            costmap.attach(m, s, cps[s], outs[s][0].ptr, outs[s][1].ptr)
+        with pytest.raises(jn.JnError):
+            costmap.attach(m, 8, cps[0], outs[0][0].ptr, outs[0][1].ptr)
+        for rep in range(2):
+            attached = submit_all(m)
+            for s in range(S):
+                for a, b in zip(plain[s], attached[s]):
+                    assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (s, rep)
+                h, g = _standalone(sp, cps[s], B, bufs[s]["u8"], lut, bufs[s]["bins"], W, H)
+                assert np.array_equal(outs[s][0].numpy(), h) and np.array_equal(outs[s][1].numpy(), g), (s, rep)
+                assert h.sum() > 0
+                check_against_definition(sp, cps[s], attached[s][1], lut.numpy(), h, g, attached[s][2], ("sgm", s))
+        # a scan-less submit on an attached slot queues no costmap (there is no u8 map to read)
+        outs[0][0].upload(np.full((B, cps[0].cells_y, cps[0].cells_x), 0x1234, np.uint16))
+        m.submit_scan(0, B, dL[0].ptr, dR[0].ptr, W, H * W, bufs[0]["dd"].ptr)
+        m.wait(0)
+        assert (outs[0][0].numpy() == 0x1234).all()
+        costmap.attach(m, 1, None)
+        outs[1][1].upload(np.full((B, cps[1].cells_y, cps[1].cells_x), 55, np.int8))
+        submit_all(m)
+        assert (outs[1][1].numpy() == 55).all() and (outs[0][0].numpy() != 0x1234).any()
+
+
+@pytest.mark.parametrize("cost", [0, 1])
+def test_block_matching_through_the_standalone_call(jn, cost):
+    """The block matcher has no attach call: jn_obstacle_costmap on jn_bm_submit_scan's outputs after jn_bm_wait, against the definition."""
+    from jackal_navigation_amd import costmap, node
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, B = 320, 180, 2
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    pairs = [node.synth_pair(W, H, 40, 300 + t) for t in range(B)]
+    dL = DeviceArray.from_numpy(np.stack([p[0] for p in pairs])); dR = DeviceArray.from_numpy(np.stack([p[1] for p in pairs]))
+    dd = DeviceArray((B, H, W), np.int16); u8 = DeviceArray((B, H, W), np.uint8)
+    bins = DeviceArray((B, sp.bins), np.float64); meta = DeviceArray((B, 4), np.float64)
+    with jn.Bm(jn.Bm.parameters(num_disparities=64, cost_function=cost), W, H, max_batch=B) as m:
+        m.submit_scan(1, B, dL.ptr, dR.ptr, W, H * W, dd.ptr, sp, lut.ptr, u8.ptr, bins.ptr, meta.ptr)
+        m.wait(1)
+    cp = costmap.costmap_params()
+    h, g = _standalone(sp, cp, B, u8, lut, bins, W, H)
+    assert h.sum() > 0
+    check_against_definition(sp, cp, u8.numpy(), lut.numpy(), h, g, bins.numpy(), ("bm", cost))
+
+
+def test_one_rank_allreduce_changes_nothing(jn):
+    from jackal_navigation_amd import costmap, node, parallel
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, n = 200, 37, 2
+    rng = np.random.default_rng(5)
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cp = costmap.costmap_params()
+    maps = random_maps(rng, n, H, W)
+    hits, grid, bins = run_costmap(sp, cp, maps, lut)
+    dH = DeviceArray.from_numpy(hits); dG = DeviceArray.from_numpy(np.full(grid.shape, 55, np.int8)); dB = DeviceArray.from_numpy(bins)
+    comm = parallel.ScanComm(0, 1, 0, lambda raw: raw)
+    try:
+        for _ in range(2):
+            costmap.allreduce(comm, sp, cp, n, dB.ptr, dH.ptr, dG.ptr)
+            assert np.array_equal(dH.numpy(), hits) and np.array_equal(dG.numpy(), grid)
+        costmap.allreduce(comm, sp, cp, n, None, dH.ptr, dG.ptr)
+        assert np.array_equal(dH.numpy(), hits) and not (dG.numpy() == 0).any() and np.array_equal(dG.numpy() == 100, grid == 100)
+        with pytest.raises(jn.JnError):
+            costmap.allreduce(comm, sp, costmap.costmap_params(cells_x=0), n, dB.ptr, dH.ptr, dG.ptr)
+    finally:
+        comm.close()
+
+
+@pytest.fixture(scope="module")
+def fake_rccl(tmp_path_factory):
+    out = tmp_path_factory.mktemp("fake_rccl_costmap") / "libfake_rccl.so"
+    subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "mocks", "fake_rccl.cpp"), "-o", str(out), "-lrt"],
+                   check=True, capture_output=True, timeout=300)
+    yield str(out)
+    for f in glob.glob("/dev/shm/jnfake_*"):
+        try:
+            os.unlink(f)
+        except OSError:
+            pass
+
+
+@pytest.mark.timeout(420)
+def test_two_ranks_merge_their_grids(fake_rccl, tmp_path):
+    """Two rank processes on one GPU through the stand-in RCCL (2 frames of 64x64 cells = 8192 elements, its limit for one call): merged hits
+    are the element-wise maximum of the two ranks' own grids on both ranks, the grid is recomputed from them and the merged bins."""
+    from jackal_navigation_amd import costmap, node
+    procs = []
+    for r in range(2):
+        env = dict(os.environ, JN_RCCL_LIB=fake_rccl, JN_COMM_INIT_TIMEOUT_S="60", JN_COMM_TIMEOUT_MS="60000")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "mocks", "costmap_rank_worker.py"), str(r), "2", str(tmp_path)],
+                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+    t0 = time.time()
+    outs = []
+    for p in procs:
+        try:
+            outs.append(p.communicate(timeout=max(1.0, 300 - (time.time() - t0)))[0])
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise AssertionError("a rank hung:\n%s" % "\n".join(outs))
+    assert [p.returncode for p in procs] == [0, 0], outs
+    rep = [json.load(open(os.path.join(tmp_path, "report%d.json" % r))) for r in range(2)]
+    assert rep[0]["info"] == [0, 2, 0] and rep[1]["info"] == [1, 2, 0]
+    L = [{k: np.load(os.path.join(tmp_path, "%s%d.npy" % (k, r))) for k in ("local_hits", "local_grid", "local_bins", "merged_hits", "merged_grid", "merged_bins")} for r in range(2)]
+    assert not np.array_equal(L[0]["local_hits"], L[1]["local_hits"])                      # the ranks really saw different scenes
+    want = np.maximum(L[0]["local_hits"], L[1]["local_hits"])
+    assert ((L[0]["local_hits"] > L[1]["local_hits"]).any() and (L[0]["local_hits"] < L[1]["local_hits"]).any())
+    mb = np.minimum(L[0]["local_bins"], L[1]["local_bins"])
+    W, H = rep[0]["size"]
+    sp = node.scan_params(W, H)
+    cp = costmap.costmap_params(**rep[0]["cp"])
+    for r in range(2):
+        assert np.array_equal(L[r]["merged_hits"], want), r
+        assert np.array_equal(L[r]["merged_bins"], mb), r
+        for f in range(want.shape[0]):
+            g, decided = cd.classify(sp, cp, want[f], mb[f])
+            assert np.array_equal(L[r]["merged_grid"][f] == 100, g == 100) and np.array_equal(L[r]["merged_grid"][f][decided], g[decided]), (r, f)
+    assert np.array_equal(L[0]["merged_grid"], L[1]["merged_grid"])
+    assert (L[0]["merged_grid"] == 100).sum() >= max((L[r]["local_grid"] == 100).sum() for r in range(2))
