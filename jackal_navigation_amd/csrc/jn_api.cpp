@@ -50,6 +50,8 @@ namespace {
 
 // The obstacle costmap as part of a slot's scan tail (jn_elas_attach_costmap, include/jn_costmap.h)
 struct CostmapTail { bool on = false; jn_costmap_params cp = {}; uint16_t* hits = nullptr; int8_t* grid = nullptr; };
+// The sub-pixel tail of a slot's scan batch (jn_elas_attach_subpix, include/jn_subpix.h); has_cp: the costmap with the scan
+struct SubpixTail { bool on = false, has_cp = false; jn_costmap_params cp = {}; double* bins = nullptr; double* meta = nullptr; uint16_t* hits = nullptr; int8_t* grid = nullptr; };
 
 struct Job {
   int n = 0; const uint8_t* dI1 = nullptr; const uint8_t* dI2 = nullptr; int pitch = 0; int64_t stride = 0;
@@ -61,6 +63,7 @@ struct Job {
   // optional tail of the node on the same stream (jn_elas_submit_scan): u8 map + LUT scan of D1
   bool scan = false; jn_scan_params sp = {}; const uint8_t* dLut = nullptr; uint8_t* dDispU8 = nullptr; double* dBins = nullptr; double* dMeta = nullptr;
   CostmapTail cm;                                             // what was attached to the slot when the scan batch was submitted
+  SubpixTail sx;
 };
 
 enum { EV_BEGIN, EV_DESC, EV_SUPPORT, EV_D2H, EV_H2D0, EV_H2D, EV_RASTER, EV_DENSE, EV_LR, EV_SPECKLE, EV_GAP, EV_AM, EV_END, EV_COUNT };
@@ -81,6 +84,7 @@ struct Slot {
   uint32_t* mark = nullptr; uint32_t* gridbits = nullptr; TriRec* recs = nullptr;
   unsigned long long* scan_scratch = nullptr;                 // extrema of the scan tail, 4 per frame
   CostmapTail cm; uint32_t* cm_acc = nullptr; size_t cm_acc_bytes = 0;   // attached costmap and its accumulation grid [max_batch][cells] u32 (allocated by the attach call)
+  SubpixTail sx; void* sx_scratch = nullptr; size_t sx_bytes = 0;        // attached sub-pixel tail and its scratch (subpix_scratch_bytes; allocated by the attach call)
   uint8_t* st_img = nullptr; float* st_D = nullptr;           // device staging of jn_elas_submit_host: [2][max_batch] images / maps, allocated on first use
   std::vector<FrameScratch> scratch;
   std::vector<HostWorker::SideState> sides;                  // [2 * max_batch]: per frame side, for the phased (parallel) triangulation
@@ -407,6 +411,11 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
       launch_scan(st, j.sp, n, j.dD1, j.dDispU8, j.dLut, dp.W, dp.H, j.dBins, j.dMeta, s.scan_scratch, j.merge ? s.d_flat : nullptr);
     if (j.scan && j.cm.on)                                 // the obstacle costmap of the map and the bins the scan has just written, same stream
       HIP_TRY(launch_costmap(st, j.sp, j.cm.cp, n, j.dDispU8, j.dLut, dp.W, dp.H, j.dBins, s.cm_acc, j.cm.hits, j.cm.grid));
+    if (j.scan && j.sx.on) {                               // the sub-pixel tail: scan (and costmap) of the float map itself, behind everything above
+      jn_subpix_params fp;
+      jn_subpix_params_default(&fp, JN_DISP_F32);
+      launch_subpix(st, j.sp, j.sx.has_cp ? &j.sx.cp : nullptr, fp, n, j.dD1, dp.W, dp.H, j.sx.bins, j.sx.meta, j.sx.hits, j.sx.grid, s.sx_scratch);
+    }
     HIP_TRY(hipEventRecord(s.ev[EV_END], st));
     return JN_OK;
   };
@@ -918,7 +927,7 @@ void jn_elas_destroy(jn_elas* h) {
   hipSetDevice(h->device);
   for (auto& s : h->slots) {
     hipFree(s->desc); hipFree(s->planes); hipFree(s->d_can); hipFree(s->info); hipFree(s->payload);
-    hipFree(s->bin_count); hipFree(s->bin_list); hipFree(s->raw); hipFree(s->tmp); hipFree(s->label); hipFree(s->size); hipFree(s->scan_scratch); hipFree(s->cm_acc); hipFree(s->d_flat); hipFree(s->st_img); hipFree(s->st_D); hipFree(s->arr_scratch);
+    hipFree(s->bin_count); hipFree(s->bin_list); hipFree(s->raw); hipFree(s->tmp); hipFree(s->label); hipFree(s->size); hipFree(s->scan_scratch); hipFree(s->cm_acc); hipFree(s->sx_scratch); hipFree(s->d_flat); hipFree(s->st_img); hipFree(s->st_D); hipFree(s->arr_scratch);
     hipFree(s->mark); hipFree(s->gridbits); hipFree(s->recs);
     hipHostFree(s->h_can); hipHostFree(s->h_info); hipHostFree(s->h_payload); hipHostFree(s->h_list); hipHostFree(s->h_cnt); hipHostFree(s->h_arr); hipHostFree(s->h_arr_ok);
     for (int e = 0; e < EV_COUNT; e++) if (s->ev[e]) hipEventDestroy(s->ev[e]);
@@ -989,6 +998,7 @@ jn_status jn_elas_submit_scan(jn_elas* h, int32_t slot, int32_t n, const uint8_t
     s.job = Job{n, dI1, dI2, pitch, image_stride, dD1, dD2, status};
     s.job.scan = true; s.job.sp = *sp; s.job.dLut = dLut; s.job.dDispU8 = dDispU8; s.job.dBins = dBins; s.job.dMeta = dMeta;
     s.job.cm = s.cm;
+    s.job.sx = s.sx;
     {
       std::lock_guard<std::mutex> g(h->merge_m);             // the submitting thread numbers the batches: same order on every rank
       if (h->comm) { s.job.merge = true; s.job.seq = h->submit_seq++; }
@@ -1014,6 +1024,27 @@ jn_status jn_elas_attach_costmap(jn_elas* h, int32_t slot, const jn_costmap_para
     s.cm_acc_bytes = need;
   }
   s.cm.on = true; s.cm.cp = *cp; s.cm.hits = dHits; s.cm.grid = dGrid;
+  return JN_OK;
+}
+
+jn_status jn_elas_attach_subpix(jn_elas* h, int32_t slot, const jn_costmap_params* cp, double* dBins, double* dMeta, uint16_t* dHits, int8_t* dGrid) {
+  if (!h || slot < 0 || slot >= (int)h->slots.size()) return JN_ERR_INVALID;
+  const bool detach = !cp && !dBins && !dMeta && !dHits && !dGrid;
+  if (!detach && (!dBins || !dMeta || (cp ? (!costmap_params_valid(cp) || !dHits || !dGrid) : (dHits || dGrid)))) return JN_ERR_INVALID;
+  Slot& s = *h->slots[slot];
+  std::unique_lock<std::mutex> l(s.m);
+  s.cv.wait(l, [&] { return !s.busy; });                    // no batch in flight on the slot
+  if (detach) { s.sx = SubpixTail(); return JN_OK; }
+  const size_t need = subpix_scratch_bytes(cp, h->max_batch);
+  if (need > s.sx_bytes) {                                  // grow-only; the slot is idle, nothing reads the old scratch
+    HIP_TRY(hipSetDevice(h->device));
+    if (s.sx_scratch) { hipFree(s.sx_scratch); s.sx_scratch = nullptr; s.sx_bytes = 0; }
+    HIP_TRY(hipMalloc(&s.sx_scratch, need));
+    s.sx_bytes = need;
+  }
+  s.sx = SubpixTail();
+  s.sx.on = true; s.sx.has_cp = cp != nullptr; if (cp) s.sx.cp = *cp;
+  s.sx.bins = dBins; s.sx.meta = dMeta; s.sx.hits = dHits; s.sx.grid = dGrid;
   return JN_OK;
 }
 

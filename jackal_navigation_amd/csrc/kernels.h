@@ -5,6 +5,7 @@
 #include "jn_types.h"
 #include "../../include/jn_stereo.h"
 #include "../../include/jn_costmap.h"
+#include "../../include/jn_subpix.h"
 
 namespace jnav {
 
@@ -141,5 +142,16 @@ void launch_costmap_finish(hipStream_t st, const jn_scan_params& sp, const jn_co
                            const double* bins, int8_t* grid);
 // Cross-rig merge: hits -> negated doubles in `flat` [count], or back (+inf -> 0).
 void launch_costmap_pack(hipStream_t st, long long count, uint16_t* hits, double* flat, bool pack);
+
+// Sub-pixel navigation tail (include/jn_subpix.h; subpix.hip) -----------------------------------------
+bool subpix_params_valid(const jn_subpix_params* fp);
+size_t subpix_scratch_bytes(const jn_costmap_params* cp, int n);      // extrema [n][4] u64, then (cp != nullptr) acc: one u32 per cell and frame
+// Initialisation, the pass over the pixels and the finish, all on `st`: disp [n][H][W] in fp.format -> bins [n][sp.bins], meta [n][4] and,
+// with cp != nullptr, hits / grid [n][cells_y][cells_x] (costmap.hip's finish kernel).  Nothing here can fail short of a launch error.
+void launch_subpix(hipStream_t st, const jn_scan_params& sp, const jn_costmap_params* cp, const jn_subpix_params& fp, int n, const void* disp,
+                   int W, int H, double* bins, double* meta, uint16_t* hits, int8_t* grid, void* scratch);
+// col_count: [W+1] int64 scratch
+void launch_subpix_point_cloud(hipStream_t st, const jn_scan_params& sp, const jn_subpix_params& fp, const void* disp, int W, int H, float* xyz,
+                               long long* col_count);
 
 }  // namespace jnav

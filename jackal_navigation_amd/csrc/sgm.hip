@@ -13,8 +13,9 @@
 #include <cstring>
 #include "../../include/jn_sgm.h"
 #include "../../include/jn_costmap.h"
+#include "../../include/jn_subpix.h"
 #include "sgm_sweep.h"
-#include "kernels.h"            // launch_scan, launch_costmap: the node's tail on a slot's stream (jn_sgm_submit_scan)
+#include "kernels.h"            // launch_scan, launch_costmap, launch_subpix: the node's tails on a slot's stream (jn_sgm_submit_scan)
 
 namespace {
 
@@ -50,6 +51,10 @@ struct jn_sgm {
   // the obstacle costmap as part of a slot's scan tail (jn_sgm_attach_costmap, include/jn_costmap.h): acc [max_batch][cells] u32, allocated by the attach call
   struct Costmap { bool on = false; jn_costmap_params cp = {}; uint16_t* hits = nullptr; int8_t* grid = nullptr; uint32_t* acc = nullptr; size_t acc_bytes = 0; };
   Costmap costmap[kSgmSlots];
+  // the sub-pixel tail of a slot's scan batch (jn_sgm_attach_subpix, include/jn_subpix.h); scratch allocated by the attach call
+  struct Subpix { bool on = false, has_cp = false; jn_costmap_params cp = {}; double* bins = nullptr; double* meta = nullptr; uint16_t* hits = nullptr; int8_t* grid = nullptr;
+                  void* scratch = nullptr; size_t scratch_bytes = 0; };
+  Subpix subpix[kSgmSlots];
   static_assert(kSgmSlots == sizeof(ev_end) / sizeof(ev_end[0]), "one end event per slot");
 };
 
@@ -81,6 +86,7 @@ void jn_sgm_destroy(jn_sgm* h) {
   }
   for (auto& q : h->scan_scratch) hipFree(q);
   for (auto& c : h->costmap) hipFree(c.acc);
+  for (auto& x : h->subpix) hipFree(x.scratch);
   jnav_sgm::sweep_release(h->sb);
   hipFree(h->sb.gm); hipFree(h->sb.volF); hipFree(h->sb.volH0); hipFree(h->sb.volH1); hipFree(h->sb.gx); hipFree(h->sb.flags); hipFree(h->sb.minr); hipFree(h->sb.dl);
   for (auto& e : h->ev) if (e) hipEventDestroy(e);
@@ -202,6 +208,12 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
     const jn_sgm::Costmap& c = h->costmap[slot];
     SGM_TRY(jnav::launch_costmap(st, *sp, c.cp, n, dDispU8, dLut, h->W, h->H, dBins, c.acc, c.hits, c.grid));
   }
+  if (sp && h->subpix[slot].on) {                               // the sub-pixel tail, from the int16 map: behind the tail kernel that writes it (the fused k_scan)
+    const jn_sgm::Subpix& x = h->subpix[slot];
+    jn_subpix_params fp;
+    jn_subpix_params_default(&fp, h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16);
+    jnav::launch_subpix(st, *sp, x.has_cp ? &x.cp : nullptr, fp, n, dDisp, h->W, h->H, x.bins, x.meta, x.hits, x.grid, x.scratch);
+  }
   // the batch's end: behind the scan tail, not behind the sweeps (ev[3] stays the end of the winner-takes-all timing)
   if (!h->ev_end[slot]) SGM_TRY(hipEventCreateWithFlags(&h->ev_end[slot], hipEventDisableTiming));
   SGM_TRY(hipEventRecord(h->ev_end[slot], st));
@@ -224,6 +236,25 @@ jn_status jn_sgm_attach_costmap(jn_sgm* h, int32_t slot, const jn_costmap_params
     c.acc_bytes = need;
   }
   c.on = true; c.cp = *cp; c.hits = dHits; c.grid = dGrid;
+  return JN_OK;
+}
+
+jn_status jn_sgm_attach_subpix(jn_sgm* h, int32_t slot, const jn_costmap_params* cp, double* dBins, double* dMeta, uint16_t* dHits, int8_t* dGrid) {
+  if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
+  const bool detach = !cp && !dBins && !dMeta && !dHits && !dGrid;
+  if (!detach && (!dBins || !dMeta || (cp ? (!jnav::costmap_params_valid(cp) || !dHits || !dGrid) : (dHits || dGrid)))) return JN_ERR_INVALID;
+  if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
+  jn_sgm::Subpix& x = h->subpix[slot];
+  if (detach) { x.on = false; x.has_cp = false; x.bins = x.meta = nullptr; x.hits = nullptr; x.grid = nullptr; return JN_OK; }
+  const size_t need = jnav::subpix_scratch_bytes(cp, h->max_batch);
+  if (need > x.scratch_bytes) {                                 // grow-only; the slot is idle, nothing reads the old scratch
+    SGM_TRY(hipSetDevice(h->device));
+    if (x.scratch) { hipFree(x.scratch); x.scratch = nullptr; x.scratch_bytes = 0; }
+    SGM_TRY(hipMalloc(&x.scratch, need));
+    x.scratch_bytes = need;
+  }
+  x.on = true; x.has_cp = cp != nullptr; if (cp) x.cp = *cp;
+  x.bins = dBins; x.meta = dMeta; x.hits = dHits; x.grid = dGrid;
   return JN_OK;
 }
 

@@ -97,6 +97,11 @@ class Elas:
         _lib.check(self._L.jn_elas_submit_scan(self._h, slot, n, dI1, dI2, pitch, image_stride, dD1, dD2, C.byref(sp), dLut,
                                                dDispU8, dBins, dMeta, status), "jn_elas_submit_scan")
 
+    def attach_subpix(self, slot, cp=None, dBins=None, dMeta=None, dHits=None, dGrid=None):
+        """The sub-pixel tail (include/jn_subpix.h) behind every scan batch of `slot`, from the float map dD1; everything None detaches."""
+        from . import subpix
+        subpix.attach(self, slot, cp, dBins, dMeta, dHits, dGrid)
+
     def set_comm(self, comm):
         """Attach a parallel.ScanComm (or None): scan batches then end with the cross-rig MIN reduce (jn_elas_set_comm)."""
         _lib.check(self._L.jn_elas_set_comm(self._h, comm._h if comm is not None else None), "jn_elas_set_comm")

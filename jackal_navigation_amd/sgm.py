@@ -66,6 +66,11 @@ class Sgm:
         _lib.check(self._L.jn_sgm_submit_scan(self._h, slot, n, dI1, dI2, pitch, image_stride, dDisp,
                                               C.byref(scan_params) if scan_params is not None else None, dLut, dU8, dBins, dMeta), "jn_sgm_submit_scan")
 
+    def attach_subpix(self, slot, cp=None, dBins=None, dMeta=None, dHits=None, dGrid=None):
+        """The sub-pixel tail (include/jn_subpix.h) behind every scan batch of `slot`, from the int16 map; everything None detaches."""
+        from . import subpix
+        subpix.attach(self, slot, cp, dBins, dMeta, dHits, dGrid)
+
     def wait(self, slot):
         _lib.check(self._L.jn_sgm_wait(self._h, slot), "jn_sgm_wait")
 

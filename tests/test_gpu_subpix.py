@@ -1,0 +1,455 @@
+"""The sub-pixel navigation tail (include/jn_subpix.h) on the GPU against its scalar definition (tests/subpix_def.py) and against the
+entry points it is anchored in: hits, occupied cells and the cloud bit-identical; the scan bins equal wherever a pixel's atan2 does not
+decide its bin, and bit-identical (device against device) to jn_obstacle_scan_cloud / jn_obstacle_costmap / jn_point_cloud on integer
+maps; the attached form on the ELAS and SGM slots; the block matcher through the synchronous call; the cross-rig merge."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import subpix_def as sd
+
+pytestmark = pytest.mark.gpu
+
+SCAN_TOL = 1e-4                       # device atan2 / sqrt against numpy's: what the existing scan tests allow
+FORMATS = (sd.F32, sd.I16, sd.I16_SUB)
+
+
+def tweak_w0(sp):
+    """Disparity 7 gets homogeneous w = Q[14] * 7 + Q[15] = 0 exactly (the other terms of that row are 0)."""
+    sp.Q[15] = -(sp.Q[14] * 7.0)
+    return sp
+
+
+def random_q(rng, n, H, W):
+    """q in 1/16 pixel: fractional noise, faces of constant disparity (the runs the kernel keeps in registers), invalid pixels, pixels at
+    q = 112 (w = 0 under tweak_w0), values around the default min_q."""
+    q = rng.integers(-40, 2200, (n, H, W))
+    for f in range(n):
+        for _ in range(12):
+            x0, x1 = sorted(rng.integers(0, W, 2)); y0, y1 = sorted(rng.integers(0, H, 2))
+            q[f, y0:y1 + 1, x0:x1 + 1] = rng.integers(40, 1900)
+    special = rng.random((n, H, W))
+    for v, lo in ((-16, 0.00), (31, 0.04), (32, 0.08), (112, 0.12), (33, 0.16)):
+        q[(special >= lo) & (special < lo + 0.04)] = v
+    return q
+
+
+def as_format(q, fmt, rng=None):
+    """q (1/16 pixel, int) -> an array of the format whose to_q gives q back (I16: q is made a multiple of 16 first)."""
+    if fmt == sd.F32:
+        a = (q.astype(np.float64) / 16.0).astype(np.float32)
+        if rng is not None:                                      # below the rounding step: rint(16 d) must not move
+            a = (a.astype(np.float64) + (rng.random(q.shape) - 0.5) * 0.05).astype(np.float32)
+        return a
+    if fmt == sd.I16:
+        return np.floor_divide(q, 16).astype(np.int16)
+    return q.astype(np.int16)
+
+
+def run(sp, cp, fp, maps, want_cloud=True):
+    """maps [n][H][W] -> dict of numpy outputs of jn_subpix_costmap, jn_subpix_scan and jn_subpix_point_cloud (first map)."""
+    from jackal_navigation_amd import subpix
+    from jackal_navigation_amd.device import DeviceArray
+    n, H, W = maps.shape
+    dD = DeviceArray.from_numpy(maps)
+    out = {}
+    bins = DeviceArray.from_numpy(np.full((n, sp.bins), 77.0)); meta = DeviceArray.from_numpy(np.full((n, 4), 77.0))
+    subpix.subpix_scan(sp, fp, n, dD.ptr, W, H, bins.ptr, meta.ptr)
+    out["scan_bins"], out["scan_meta"] = bins.numpy(), meta.numpy()
+    if cp is not None:
+        bins2 = DeviceArray.from_numpy(np.full((n, sp.bins), 55.0)); meta2 = DeviceArray.from_numpy(np.full((n, 4), 55.0))
+        hits = DeviceArray.from_numpy(np.full((n, cp.cells_y, cp.cells_x), 0xABCD, np.uint16))
+        grid = DeviceArray.from_numpy(np.full((n, cp.cells_y, cp.cells_x), 77, np.int8))
+        subpix.subpix_costmap(sp, cp, fp, n, dD.ptr, W, H, bins2.ptr, meta2.ptr, hits.ptr, grid.ptr)
+        out.update(bins=bins2.numpy(), meta=meta2.numpy(), hits=hits.numpy(), grid=grid.numpy())
+    if want_cloud:
+        out["cloud"] = subpix.subpix_point_cloud(sp, fp, dD.ptr, W, H)
+    return out
+
+
+def check_against_definition(sp, cp, fp, maps, out, what):
+    n = maps.shape[0]
+    if "bins" in out:                                             # the costmap call's scan IS the scan call's
+        assert np.array_equal(out["bins"], out["scan_bins"]) and np.array_equal(out["meta"], out["scan_meta"]), what
+    for f in range(n):
+        q, valid = sd.to_q(maps[f], fp.format, fp.min_q)
+        bins, meta, edge = sd.scan(sp, q, valid)
+        got = out["scan_bins"][f]
+        if edge > 1e-9:                                            # no pixel's bin hangs on the last bits of its atan2
+            assert np.array_equal(got < sd.EMPTY - 1, bins < sd.EMPTY - 1), (what, f)
+            assert np.allclose(got, bins, rtol=0, atol=SCAN_TOL), (what, f)
+        assert np.allclose(out["scan_meta"][f], meta, rtol=0, atol=SCAN_TOL), (what, f)
+        if cp is not None:
+            want = sd.hits(sp, cp, q, valid)
+            assert np.array_equal(out["hits"][f], want), (what, f, int((out["hits"][f] != want).sum()))
+            g, decided = sd.classify(sp, cp, want, out["bins"][f])
+            assert np.array_equal(out["grid"][f] == 100, g == 100), (what, f)
+            assert set(np.unique(out["grid"][f])) <= {-1, 0, 100}, (what, f)
+            assert np.array_equal(out["grid"][f][decided], g[decided]), (what, f)
+    if "cloud" in out:
+        q, valid = sd.to_q(maps[0], fp.format, fp.min_q)
+        want = sd.cloud(sp, q, valid)
+        assert out["cloud"].shape == want.shape and np.array_equal(out["cloud"].view(np.uint32), want.view(np.uint32)), what
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("W,H,n", [(320, 180, 3), (1280, 720, 2), (1919, 1079, 1)])
+def test_random_maps_equal_the_definition(jn, fmt, W, H, n):
+    from jackal_navigation_amd import costmap, node, subpix
+    rng = np.random.default_rng(100 + fmt + W)
+    sp = tweak_w0(node.scan_params(W, H))
+    sp.crop_offset_x, sp.crop_offset_y = 5, 3
+    cp = costmap.costmap_params(min_hits=2, from_cloud=1 if fmt == sd.I16 else 0)          # from_cloud is ignored
+    fp = subpix.subpix_params(fmt)
+    maps = as_format(random_q(rng, n, H, W), fmt, rng)
+    out = run(sp, cp, fp, maps)
+    check_against_definition(sp, cp, fp, maps, out, (fmt, W, H))
+    assert out["hits"].sum() > 0 and (out["grid"] == 100).any() and (out["scan_bins"] < sd.EMPTY - 1).any()
+    assert out["cloud"].shape[0] == int(sd.to_q(maps[0], fmt)[1].sum()) and (out["cloud"] == 0).all(axis=1).any()      # the w = 0 pixels
+    # n = 1 gives frame 0 of the batch; twice the same call gives the same bits
+    one = run(sp, cp, fp, maps[:1], want_cloud=False)
+    again = run(sp, cp, fp, maps[:1], want_cloud=False)
+    for k in ("scan_bins", "scan_meta", "hits", "grid"):
+        assert np.array_equal(one[k][0].view(np.uint8), out[k][0].view(np.uint8)), k
+        assert np.array_equal(one[k].view(np.uint8), again[k].view(np.uint8)), k
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("bins", [1, 90, 1024])
+def test_bin_counts_and_min_q_edges(jn, fmt, bins):
+    from jackal_navigation_amd import costmap, node, subpix
+    W, H, n = 200, 37, 2                                       # neither a multiple of the kernel's 256 columns nor of its 16 rows
+    rng = np.random.default_rng(7 * bins + fmt)
+    sp = node.scan_params(W, H)
+    sp.bins = bins
+    cp = costmap.costmap_params(cells_x=7, cells_y=13, resolution=0.31, origin_x=0.2, origin_y=-2.0, min_hits=1)
+    maps = as_format(random_q(rng, n, H, W), fmt)
+    for min_q in (0, 31, 32, 33, 48, 16 * 4096):
+        fp = subpix.subpix_params(fmt, min_q=min_q)
+        out = run(sp, cp, fp, maps)
+        check_against_definition(sp, cp, fp, maps, out, (fmt, bins, min_q))
+    assert out["hits"].sum() == 0 and out["cloud"].shape[0] == 0          # nothing reaches 4096 px
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_an_all_invalid_map(jn, fmt):
+    """Meta keeps its initial values, every bin is empty, no cell is hit and none is free, the cloud is empty."""
+    from jackal_navigation_amd import costmap, node, subpix
+    W, H = 320, 180
+    sp, cp, fp = node.scan_params(W, H), costmap.costmap_params(), subpix.subpix_params(fmt)
+    fill = {sd.F32: -10.0, sd.I16: -1, sd.I16_SUB: -16}[fmt]
+    maps = np.full((2, H, W), fill, sd_dtype(fmt))
+    if fmt == sd.F32:
+        maps[1, ::3] = np.nan; maps[1, 1::3] = np.inf
+    out = run(sp, cp, fp, maps)
+    assert (out["scan_bins"] == sd.EMPTY).all() and (out["bins"] == sd.EMPTY).all()
+    assert out["scan_meta"].tolist() == [[400.0, -400.0, 1e9, -500.0]] * 2 and np.array_equal(out["meta"], out["scan_meta"])
+    assert (out["hits"] == 0).all() and (out["grid"] == -1).all() and out["cloud"].shape == (0, 3)
+
+
+def sd_dtype(fmt):
+    return np.float32 if fmt == sd.F32 else np.int16
+
+
+def integer_maps(rng, n, H, W):
+    m = rng.integers(2, 256, (n, H, W)).astype(np.uint8)
+    for f in range(n):
+        for _ in range(10):
+            x0, x1 = sorted(rng.integers(0, W, 2)); y0, y1 = sorted(rng.integers(0, H, 2))
+            m[f, y0:y1 + 1, x0:x1 + 1] = rng.integers(3, 120)
+    return m
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("W,H", [(320, 180), (641, 353)])
+def test_the_anchor_on_the_device(jn, fmt, W, H):
+    """Integer maps: bins, meta, hits, grid and cloud are the bits jn_obstacle_scan_cloud, jn_obstacle_costmap(from_cloud = 1) and
+    jn_point_cloud produce from the u8 map of the same values."""
+    from jackal_navigation_amd import costmap, node, subpix
+    from jackal_navigation_amd.device import DeviceArray
+    n = 2
+    rng = np.random.default_rng(31 + fmt)
+    sp = tweak_w0(node.scan_params(W, H))
+    sp.crop_offset_x, sp.crop_offset_y = 2, 9
+    cp = costmap.costmap_params(from_cloud=1, min_hits=2)
+    u8 = integer_maps(rng, n, H, W)
+    assert (u8 == 7).any()
+    dU = DeviceArray.from_numpy(u8)
+    bins = DeviceArray((n, sp.bins), np.float64); meta = DeviceArray((n, 4), np.float64)
+    node.obstacle_scan_cloud(sp, n, dU.ptr, W, H, bins.ptr, meta.ptr)
+    hits = DeviceArray((n, cp.cells_y, cp.cells_x), np.uint16); grid = DeviceArray((n, cp.cells_y, cp.cells_x), np.int8)
+    costmap.obstacle_costmap(sp, cp, n, dU.ptr, None, W, H, bins.ptr, hits.ptr, grid.ptr)
+    cloud = node.point_cloud(sp, dU.ptr, W, H)
+    maps = {sd.F32: u8.astype(np.float32), sd.I16: u8.astype(np.int16), sd.I16_SUB: u8.astype(np.int16) * 16}[fmt]
+    out = run(sp, cp, subpix.subpix_params(fmt), maps)
+    assert (bins.numpy() < sd.EMPTY - 1).sum() > 20 and hits.numpy().sum() > 0
+    for got, want in ((out["bins"], bins.numpy()), (out["meta"], meta.numpy()), (out["scan_bins"], bins.numpy()), (out["scan_meta"], meta.numpy()),
+                      (out["hits"], hits.numpy()), (out["grid"], grid.numpy()), (out["cloud"], cloud)):
+        assert got.shape == want.shape and np.array_equal(got.view(np.uint8), want.view(np.uint8))
+
+
+def test_counts_saturate_at_65535_and_min_hits_edge(jn):
+    """One 100 m cell collects a whole 640x480 frame of obstacle pixels: 307200 of them, stored as 65535; min_hits on both sides of a count."""
+    from jackal_navigation_amd import costmap, node, subpix
+    W, H = 640, 480
+    sp = node.scan_params(W, H)
+    sp.gp_height_thresh = -1e9                                # no point is ground
+    maps = np.full((2, H, W), 40 * 16 + 5, np.int16)
+    maps[1, :100] = -16                                       # 243200 obstacle pixels in the second frame
+    maps[1, 100:, 150:] = -16                                 # ... 57000: below the limit
+    fp = subpix.subpix_params(sd.I16_SUB)
+    for min_hits, occ in ((57000, 100), (57001, -1)):
+        cp = costmap.costmap_params(cells_x=1, cells_y=1, resolution=100.0, origin_x=-50.0, origin_y=-50.0, min_hits=min_hits)
+        out = run(sp, cp, fp, maps, want_cloud=False)
+        assert out["hits"][0, 0, 0] == 65535 and out["hits"][1, 0, 0] == 380 * 150
+        assert out["grid"][0, 0, 0] == 100 and out["grid"][1, 0, 0] == occ
+        check_against_definition(sp, cp, fp, maps, out, ("saturation", min_hits))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_free_cells_in_front_of_a_far_wall(jn, fmt):
+    """A wall a few metres away at a fractional disparity (a nearer post in the second frame): free in front, unknown behind and outside
+    the fan, and all three values equal the definition's away from bin edges (tests/test_gpu_costmap.py's rule)."""
+    from jackal_navigation_amd import costmap, node, subpix
+    W, H = 320, 180
+    sp, cp, fp = node.scan_params(W, H), costmap.costmap_params(), subpix.subpix_params(fmt)
+    q = np.full((2, H, W), 5 * 16 + (0 if fmt == sd.I16 else 7), np.int64)
+    q[1, :, 100:130] = 14 * 16 + (0 if fmt == sd.I16 else 11)
+    maps = as_format(q, fmt)
+    out = run(sp, cp, fp, maps, want_cloud=False)
+    check_against_definition(sp, cp, fp, maps, out, ("wall", fmt))
+    for f in range(2):
+        g = out["grid"][f]
+        assert (g == 0).sum() > 500 and (g == -1).sum() > 500 and (g == 100).any(), f
+    assert (out["grid"][0] == 0).sum() > (out["grid"][1] == 0).sum()        # the post shadows the cells behind it
+
+
+def _sync(sp, cp, fmt, n, dDisp, W, H):
+    """The synchronous call on a device map: what an attached tail must equal."""
+    from jackal_navigation_amd import subpix
+    from jackal_navigation_amd.device import DeviceArray
+    fp = subpix.subpix_params(fmt)
+    bins = DeviceArray((n, sp.bins), np.float64); meta = DeviceArray((n, 4), np.float64)
+    if cp is None:
+        subpix.subpix_scan(sp, fp, n, dDisp.ptr, W, H, bins.ptr, meta.ptr)
+        return bins.numpy(), meta.numpy(), None, None
+    hits = DeviceArray((n, cp.cells_y, cp.cells_x), np.uint16); grid = DeviceArray((n, cp.cells_y, cp.cells_x), np.int8)
+    subpix.subpix_costmap(sp, cp, fp, n, dDisp.ptr, W, H, bins.ptr, meta.ptr, hits.ptr, grid.ptr)
+    return bins.numpy(), meta.numpy(), hits.numpy(), grid.numpy()
+
+
+class Outs:
+    """Poisoned output buffers of one attached tail."""
+
+    def __init__(self, B, sp, cp):
+        from jackal_navigation_amd.device import DeviceArray
+        self.B, self.sp, self.cp = B, sp, cp
+        self.bins = DeviceArray((B, sp.bins), np.float64); self.meta = DeviceArray((B, 4), np.float64)
+        self.hits = DeviceArray((B, cp.cells_y, cp.cells_x), np.uint16) if cp is not None else None
+        self.grid = DeviceArray((B, cp.cells_y, cp.cells_x), np.int8) if cp is not None else None
+        self.poison()
+
+    def poison(self):
+        self.bins.upload(np.full(self.bins.shape, 12345.0)); self.meta.upload(np.full(self.meta.shape, 12345.0))
+        if self.cp is not None:
+            self.hits.upload(np.full(self.hits.shape, 0x1234, np.uint16)); self.grid.upload(np.full(self.grid.shape, 55, np.int8))
+
+    def ptrs(self):
+        return (self.bins.ptr, self.meta.ptr, self.hits.ptr if self.cp is not None else None, self.grid.ptr if self.cp is not None else None)
+
+    def numpy(self):
+        return (self.bins.numpy(), self.meta.numpy(), self.hits.numpy() if self.cp is not None else None,
+                self.grid.numpy() if self.cp is not None else None)
+
+    def untouched(self):
+        ok = (self.bins.numpy() == 12345.0).all() and (self.meta.numpy() == 12345.0).all()
+        if self.cp is not None:
+            ok = ok and (self.hits.numpy() == 0x1234).all() and (self.grid.numpy() == 55).all()
+        return bool(ok)
+
+
+def same_outputs(a, b):
+    return all((x is None and y is None) or np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a, b))
+
+
+def test_attached_to_elas_slots(jn):
+    """Two slots in flight, one with scan + costmap attached (next to an attached jn_costmap) and one with the scan only, a failing frame
+    in slot 1's batch: each slot's outputs equal the synchronous call on that slot's dD1; the ordinary outputs are those of a handle with
+    nothing attached; after detaching the buffers are no longer written."""
+    from jackal_navigation_amd import costmap, node, subpix
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, B, S = 320, 180, 2, 2
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cp = costmap.costmap_params(min_hits=2)
+    pairs = [[node.synth_pair(W, H, 30 + 9 * s, 40 + 10 * s + t) for t in range(B)] for s in range(S)]
+    flat = np.full((H, W), 90, np.uint8)
+    pairs[1][1] = (flat, flat)                                                       # no texture: this frame fails, its dD1 stays as it was
+    dL = [DeviceArray.from_numpy(np.stack([p[0] for p in ps])) for ps in pairs]
+    dR = [DeviceArray.from_numpy(np.stack([p[1] for p in ps])) for ps in pairs]
+    rng = np.random.default_rng(9)
+    before = (rng.integers(0, 400, (B, H, W)) / 16.0).astype(np.float32)           # what dD1 holds beforehand
+    bufs = [dict(d1=DeviceArray((B, H, W), np.float32), d2=DeviceArray((B, H, W), np.float32), u8=DeviceArray((B, H, W), np.uint8),
+                 bins=DeviceArray((B, sp.bins), np.float64), meta=DeviceArray((B, 4), np.float64), st=(C.c_int32 * B)(),
+                 hits=DeviceArray((B, cp.cells_y, cp.cells_x), np.uint16), grid=DeviceArray((B, cp.cells_y, cp.cells_x), np.int8)) for _ in range(S)]
+
+    def submit_all(e):
+        for s in range(S):
+            bufs[s]["d1"].upload(before); bufs[s]["d2"].upload(before)
+        for s in range(S):
+            b = bufs[s]
+            e.submit_scan(s, B, dL[s].ptr, dR[s].ptr, W, H * W, b["d1"].ptr, b["d2"].ptr, sp, lut.ptr, b["u8"].ptr, b["bins"].ptr, b["meta"].ptr, b["st"])
+        for s in range(S):
+            e.wait(s)
+        return [tuple(bufs[s][k].numpy().copy() for k in ("d1", "d2", "u8", "bins", "meta", "hits", "grid")) + (list(bufs[s]["st"]),) for s in range(S)]
+
+    with jn.Elas(jn.Elas.parameters(0), W, H, max_batch=B, slots=S, host_threads=4) as e:
+        for s in range(S):
+            costmap.attach(e, s, cp, bufs[s]["hits"].ptr, bufs[s]["grid"].ptr)
+        plain = submit_all(e)
+        assert plain[0][7] == [0, 0] and plain[1][7][0] == 0 and plain[1][7][1] != 0
+        assert np.array_equal(plain[1][0][1], before[1])                             # the failed frame's dD1 is untouched
+        outs = [Outs(B, sp, cp), Outs(B, sp, None)]
+        e.attach_subpix(0, cp, *outs[0].ptrs())
+        subpix.attach(e, 1, None, *outs[1].ptrs())
+        for bad in ((S, cp) + outs[0].ptrs(), (-1, cp) + outs[0].ptrs(), (0, cp, None) + outs[0].ptrs()[1:], (0, cp, outs[0].bins.ptr, None) + outs[0].ptrs()[2:],
+                    (0, cp, outs[0].bins.ptr, outs[0].meta.ptr, None, outs[0].grid.ptr), (0, None, outs[0].bins.ptr, outs[0].meta.ptr, outs[0].hits.ptr, None),
+                    (0, costmap.costmap_params(cells_x=0)) + outs[0].ptrs()):
+            with pytest.raises(jn.JnError):
+                e.attach_subpix(*bad)
+        for rep in range(2):                                                         # twice: the scratch is initialised per batch
+            for o in outs:
+                o.poison()
+            attached = submit_all(e)
+            for s in range(S):
+                for a, b in zip(plain[s][:7], attached[s][:7]):
+                    assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (s, rep)
+                assert plain[s][7] == attached[s][7]
+                want = _sync(sp, outs[s].cp, sd.F32, B, bufs[s]["d1"], W, H)
+                assert same_outputs(outs[s].numpy(), want), (s, rep)
+                assert (want[0] < sd.EMPTY - 1).any()
+            got = outs[0].numpy()
+            assert got[2].sum() > 0 and (got[3] == 100).any()
+            check_against_definition(sp, cp, subpix.subpix_params(sd.F32), attached[0][0],
+                                     dict(scan_bins=got[0], scan_meta=got[1], bins=got[0], meta=got[1], hits=got[2], grid=got[3]), ("elas", rep))
+        e.attach_subpix(0)                                                           # detach slot 0
+        for o in outs:
+            o.poison()
+        detached = submit_all(e)
+        assert outs[0].untouched() and not outs[1].untouched()
+        for s in range(S):
+            for a, b in zip(plain[s][:7], detached[s][:7]):
+                assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), s
+        e.attach_subpix(1)
+
+
+@pytest.mark.parametrize("subpixel", [0, 1])
+def test_attached_to_sgm_slots(jn, subpixel):
+    from jackal_navigation_amd import costmap, node, subpix
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, B, S = 320, 180, 2, 2
+    fmt = sd.I16_SUB if subpixel else sd.I16
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    cp = costmap.costmap_params(min_hits=2)
+    pairs = [[node.synth_pair(W, H, 28 + 11 * s, 90 + 10 * s + t) for t in range(B)] for s in range(S)]
+    dL = [DeviceArray.from_numpy(np.stack([p[0] for p in ps])) for ps in pairs]
+    dR = [DeviceArray.from_numpy(np.stack([p[1] for p in ps])) for ps in pairs]
+    bufs = [dict(dd=DeviceArray((B, H, W), np.int16), u8=DeviceArray((B, H, W), np.uint8), bins=DeviceArray((B, sp.bins), np.float64),
+                 meta=DeviceArray((B, 4), np.float64), hits=DeviceArray((B, cp.cells_y, cp.cells_x), np.uint16),
+                 grid=DeviceArray((B, cp.cells_y, cp.cells_x), np.int8)) for _ in range(S)]
+
+    def submit_all(m):
+        for s in range(S):
+            b = bufs[s]
+            m.submit_scan(s, B, dL[s].ptr, dR[s].ptr, W, H * W, b["dd"].ptr, sp, lut.ptr, b["u8"].ptr, b["bins"].ptr, b["meta"].ptr)
+        for s in range(S):
+            m.wait(s)
+        return [tuple(bufs[s][k].numpy().copy() for k in ("dd", "u8", "bins", "meta", "hits", "grid")) for s in range(S)]
+
+    with jn.Sgm(jn.Sgm.parameters(num_disparities=64, subpixel=subpixel), W, H, max_batch=B) as m:
+        costmap.attach(m, 0, cp, bufs[0]["hits"].ptr, bufs[0]["grid"].ptr)
+        costmap.attach(m, 1, cp, bufs[1]["hits"].ptr, bufs[1]["grid"].ptr)
+        plain = submit_all(m)
+        if subpixel:
+            assert (plain[0][0][plain[0][0] > 0] % 16 != 0).any()                  # fractions are there to be used
+        outs = [Outs(B, sp, cp), Outs(B, sp, None)]
+        m.attach_subpix(0, cp, *outs[0].ptrs())
+        subpix.attach(m, 1, None, *outs[1].ptrs())
+        for bad in ((8, cp) + outs[0].ptrs(), (-1, cp) + outs[0].ptrs(), (0, cp, None) + outs[0].ptrs()[1:],
+                    (0, None, outs[0].bins.ptr, outs[0].meta.ptr, None, outs[0].grid.ptr), (0, costmap.costmap_params(min_hits=0)) + outs[0].ptrs()):
+            with pytest.raises(jn.JnError):
+                m.attach_subpix(*bad)
+        for rep in range(2):
+            for o in outs:
+                o.poison()
+            attached = submit_all(m)
+            for s in range(S):
+                for a, b in zip(plain[s], attached[s]):
+                    assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (s, rep)
+                want = _sync(sp, outs[s].cp, fmt, B, bufs[s]["dd"], W, H)
+                assert same_outputs(outs[s].numpy(), want), (s, rep)
+                assert (want[0] < sd.EMPTY - 1).any()
+            got = outs[0].numpy()
+            assert got[2].sum() > 0
+            check_against_definition(sp, cp, subpix.subpix_params(fmt), attached[0][0],
+                                     dict(scan_bins=got[0], scan_meta=got[1], bins=got[0], meta=got[1], hits=got[2], grid=got[3]), ("sgm", subpixel, rep))
+        # a scan-less submit on an attached slot queues no tail (there are no scan parameters to reproject with)
+        outs[0].poison()
+        m.submit_scan(0, B, dL[0].ptr, dR[0].ptr, W, H * W, bufs[0]["dd"].ptr)
+        m.wait(0)
+        assert outs[0].untouched()
+        m.attach_subpix(1)
+        for o in outs:
+            o.poison()
+        detached = submit_all(m)
+        assert outs[1].untouched() and not outs[0].untouched()
+        for s in range(S):
+            for a, b in zip(plain[s], detached[s]):
+                assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), s
+
+
+@pytest.mark.parametrize("subpixel", [0, 1])
+def test_block_matching_through_the_synchronous_call(jn, subpixel):
+    """The block matcher has no attach call: jn_subpix_costmap on jn_bm_submit_scan's dDisp after jn_bm_wait, against the definition."""
+    from jackal_navigation_amd import costmap, node, subpix
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, B = 320, 180, 2
+    fmt = sd.I16_SUB if subpixel else sd.I16
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    pairs = [node.synth_pair(W, H, 40, 300 + t) for t in range(B)]
+    dL = DeviceArray.from_numpy(np.stack([p[0] for p in pairs])); dR = DeviceArray.from_numpy(np.stack([p[1] for p in pairs]))
+    dd = DeviceArray((B, H, W), np.int16); u8 = DeviceArray((B, H, W), np.uint8)
+    bins = DeviceArray((B, sp.bins), np.float64); meta = DeviceArray((B, 4), np.float64)
+    with jn.Bm(jn.Bm.parameters(num_disparities=64, subpixel=subpixel), W, H, max_batch=B) as m:
+        m.submit_scan(1, B, dL.ptr, dR.ptr, W, H * W, dd.ptr, sp, lut.ptr, u8.ptr, bins.ptr, meta.ptr)
+        m.wait(1)
+    cp = costmap.costmap_params()
+    b, mt, h, g = _sync(sp, cp, fmt, B, dd, W, H)
+    assert h.sum() > 0 and (b < sd.EMPTY - 1).any()
+    check_against_definition(sp, cp, subpix.subpix_params(fmt), dd.numpy(), dict(scan_bins=b, scan_meta=mt, bins=b, meta=mt, hits=h, grid=g), ("bm", subpixel))
+
+
+def test_one_rank_allreduce_changes_nothing(jn):
+    """The cross-rig merge is the existing one: jn_scan_allreduce on the sub-pixel bins / meta and jn_costmap_allreduce on its hits / grid
+    leave a one-rank communicator's outputs as they are — the merge's grid recomputation is this mode's grid formula."""
+    from jackal_navigation_amd import costmap, node, parallel, subpix
+    from jackal_navigation_amd.device import DeviceArray
+    W, H, n = 200, 37, 2
+    rng = np.random.default_rng(5)
+    sp, cp, fp = node.scan_params(W, H), costmap.costmap_params(), subpix.subpix_params(sd.I16_SUB)
+    maps = as_format(random_q(rng, n, H, W), sd.I16_SUB)
+    out = run(sp, cp, fp, maps, want_cloud=False)
+    dB = DeviceArray.from_numpy(out["bins"]); dM = DeviceArray.from_numpy(out["meta"])
+    dH = DeviceArray.from_numpy(out["hits"]); dG = DeviceArray.from_numpy(np.full(out["grid"].shape, 55, np.int8))
+    comm = parallel.ScanComm(0, 1, 0, lambda raw: raw)
+    try:
+        for _ in range(2):
+            comm.merge(n, sp.bins, dB.ptr, dM.ptr)
+            costmap.allreduce(comm, sp, cp, n, dB.ptr, dH.ptr, dG.ptr)
+            assert np.array_equal(dB.numpy(), out["bins"]) and np.array_equal(dM.numpy(), out["meta"])
+            assert np.array_equal(dH.numpy(), out["hits"]) and np.array_equal(dG.numpy(), out["grid"])
+    finally:
+        comm.close()
