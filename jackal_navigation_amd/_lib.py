@@ -205,3 +205,17 @@ def _bind(path):
 def check(status, what):
     if status != JN_OK:
         raise JnError(status, what)
+
+
+def attach_tail(L, tail, handle, slot, cp, *buffers, alternative):
+    """jn_elas_attach_<tail> or jn_sgm_attach_<tail> of the bound library L, by the handle's type (costmap.attach, subpix.attach).  The
+    block matcher has no attach call: `alternative` names what its users call instead."""
+    from .elas import Elas
+    from .sgm import Sgm
+    if isinstance(handle, Elas):
+        what = "jn_elas_attach_" + tail
+    elif isinstance(handle, Sgm):
+        what = "jn_sgm_attach_" + tail
+    else:
+        raise TypeError("attach() takes an Elas or an Sgm handle; block-matching users call %s after Bm.wait()" % alternative)
+    check(getattr(L, what)(handle._h, slot, C.byref(cp) if cp is not None else None, *buffers), what)

@@ -57,16 +57,7 @@ def obstacle_costmap(sp, cp, n, dDisp, dLut, width, height, dBins, dHits, dGrid,
 def attach(handle, slot, cp, dHits=None, dGrid=None):
     """From now on every scan batch submitted on `slot` of an Elas or Sgm handle also writes its costmap into dHits / dGrid (valid after
     the slot's wait).  cp = None detaches.  No batch may be in flight on the slot."""
-    from .elas import Elas
-    from .sgm import Sgm
-    L = _bind()
-    if isinstance(handle, Elas):
-        fn, what = L.jn_elas_attach_costmap, "jn_elas_attach_costmap"
-    elif isinstance(handle, Sgm):
-        fn, what = L.jn_sgm_attach_costmap, "jn_sgm_attach_costmap"
-    else:
-        raise TypeError("attach() takes an Elas or an Sgm handle; block-matching users call obstacle_costmap() after Bm.wait()")
-    _lib.check(fn(handle._h, slot, C.byref(cp) if cp is not None else None, dHits, dGrid), what)
+    _lib.attach_tail(_bind(), "costmap", handle, slot, cp, dHits, dGrid, alternative="obstacle_costmap()")
 
 
 def allreduce(comm, sp, cp, n, dBins, dHits, dGrid):

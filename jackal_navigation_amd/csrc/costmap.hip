@@ -3,87 +3,26 @@
 // No reference counterpart; the definition is in jn_costmap.h, its scalar restatement (the checker) in tests/.  hits and the occupied
 // cells are integer results of individually rounded double arithmetic, so the bar for them is bit-exactness.
 //
-// The reprojection (ScanDev / reproject / is_ground / to_dev of kernels.hip, ~30 lines) is RESTATED here: kernels.hip is pinned by the
-// evidence set's manifest and cannot export them.  tests/test_gpu_costmap.py ties the two copies together (the cells this file bins are
-// the cells of jn_point_cloud's points).
+// The geometry (reprojection, ground model, cell of a point, bin of a bearing) and the wave-combined add are nav_tail.h's, shared with
+// subpix.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cmath>
-#include <cstdio>
-#include "kernels.h"
+#include "nav_tail.h"
 
 namespace jnav {
 namespace {
 
-#define DEV static __device__ __forceinline__
-
 struct CmDev {
-  double Q[16], XR[9], XT[3];
-  int ox, oy;
-  double gp_h, gp_tan, gp_dist, fov, pi;
-  int bins;
-  double org_x, org_y, res;
-  int cx, cy, min_hits;
+  NavGeom g;
+  NavGrid c;
+  int min_hits;
 };
-
-// pos = Q*[i+ox, j+oy, d, 1]; cam = pos.xyz/pos.w; robot = XR*cam + XT (point_cloud.cpp:237-253) — kernels.hip's reproject()
-DEV bool cm_reproject(const CmDev& s, int i, int j, int d, double& X, double& Y, double& Z) {
-  const double V0 = (double)(i + s.ox), V1 = (double)(j + s.oy), V2 = (double)d;
-  double pos[4];
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    double a = __dmul_rn(s.Q[4 * r], V0);
-    a = __dadd_rn(a, __dmul_rn(s.Q[4 * r + 1], V1));
-    a = __dadd_rn(a, __dmul_rn(s.Q[4 * r + 2], V2));
-    a = __dadd_rn(a, s.Q[4 * r + 3]);
-    pos[r] = a;
-  }
-  if (pos[3] == 0.0) return false;
-  const double cx = pos[0] / pos[3], cy = pos[1] / pos[3], cz = pos[2] / pos[3];
-  double o[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    double a = __dmul_rn(s.XR[3 * r], cx);
-    a = __dadd_rn(a, __dmul_rn(s.XR[3 * r + 1], cy));
-    a = __dadd_rn(a, __dmul_rn(s.XR[3 * r + 2], cz));
-    o[r] = __dadd_rn(a, s.XT[r]);
-  }
-  X = o[0]; Y = o[1]; Z = o[2];
-  return true;
-}
-DEV bool cm_is_ground(const CmDev& s, double X, double Z) {      // point_cloud.cpp:128-137 — kernels.hip's is_ground()
-  if (X < s.gp_dist) return Z < s.gp_h;
-  return Z < __dadd_rn(s.gp_h, __dmul_rn(s.gp_tan, X - s.gp_dist));
-}
-
-// Adds cnt to acc[cell] for every lane with `have`, equal cells of the wave combined first: the lanes of a wave are neighbouring columns
-// of one image tile and mostly hold the SAME cell (an obstacle's face) — 64 same-address atomics would serialise in the L2.  The first
-// kCombine distinct cells are summed across the wave and added once each by their first lane; what is left after that (a wave looking
-// at many cells: far, fronto-parallel clutter) goes out lane by lane.  Called by the whole wave (convergent).
-constexpr int kCombine = 4;
-DEV void cm_wave_add(bool have, int cell, uint32_t cnt, uint32_t* __restrict__ acc) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll 1
-  for (int it = 0; it < kCombine; it++) {
-    const unsigned long long m = __ballot(have);
-    if (m == 0ull) return;
-    const int leader = __ffsll((long long)m) - 1;
-    const int key = __shfl(cell, leader);
-    const bool mine = have && cell == key;
-    uint32_t sum = mine ? cnt : 0u;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
-    if (lane == leader) atomicAdd(&acc[key], sum);
-    if (mine) have = false;
-  }
-  if (have) atomicAdd(&acc[cell], cnt);
-}
 
 // Accumulate: hits per cell of one batch into acc [n][cy][cx] u32 (cleared in stream order ahead of the launch).
 // k_scan's shape: one thread per column, kCmRows rows, all of the thread's u8 / LUT loads requested together, a candidate mask, the
 // reprojection only for candidates.  An obstacle is a near-vertical surface: consecutive rows of a column carry the same disparity and
 // fall in the same cell, so a thread keeps (cell, count) in registers and emits one add per RUN of rows, not per pixel; the adds of a
-// wave are combined (cm_wave_add).  The candidate loop is wave-uniform (it runs while any lane has rows left) so that the combining
+// wave are combined (nav_wave_add).  The candidate loop is wave-uniform (it runs while any lane has rows left) so that the combining
 // sees the whole wave.
 constexpr int kCmRows = 16;
 template <bool kFromCloud>
@@ -92,7 +31,7 @@ __global__ void __launch_bounds__(256) k_costmap_accumulate(CmDev s, const uint8
   const int frame = blockIdx.z;
   const int i = blockIdx.x * 256 + threadIdx.x, j0 = blockIdx.y * kCmRows;
   const int jend = min(j0 + kCmRows, H);
-  uint32_t* __restrict__ facc = acc + (size_t)frame * s.cx * s.cy;
+  uint32_t* __restrict__ facc = acc + (size_t)frame * s.c.cx * s.c.cy;
   uint32_t u8pk[kCmRows / 4] = {};
   uint32_t cand = 0;
   if (i < W) {
@@ -124,29 +63,26 @@ __global__ void __launch_bounds__(256) k_costmap_accumulate(CmDev s, const uint8
       const uint32_t w = rr < 8 ? (rr < 4 ? u8pk[0] : u8pk[1]) : (rr < 12 ? u8pk[2] : u8pk[3]);
       const int d = (int)((w >> (8 * (rr & 3))) & 255u);
       double X = 0, Y = 0, Z = 0;
-      bool take = cm_reproject(s, i, j, d, X, Y, Z);
-      if (kFromCloud) take = take && !cm_is_ground(s, X, Z);                                      // :166-172
+      bool take = nav_reproject(s.g, i, j, (double)d, X, Y, Z);
+      if (kFromCloud) take = take && !nav_is_ground(s.g, X, Z);                                   // :166-172
       int cell = -1;
-      if (take && isfinite(X) && isfinite(Y) && isfinite(Z)) {
-        const double fx = floor((X - s.org_x) / s.res), fy = floor((Y - s.org_y) / s.res);
-        if (fx >= 0. && fx < (double)s.cx && fy >= 0. && fy < (double)s.cy) cell = (int)fy * s.cx + (int)fx;
-      }
+      if (take) cell = nav_cell(s.c, X, Y, Z);
       if (cell == cur_cell) cur_cnt++;
       else {
         if (cur_cell >= 0) { flush = true; fcell = cur_cell; fcnt = cur_cnt; }
         cur_cell = cell; cur_cnt = 1;
       }
     }
-    if (__any(flush)) cm_wave_add(flush, fcell, fcnt, facc);
+    if (__any(flush)) nav_wave_add(flush, fcell, fcnt, facc);
   }
-  cm_wave_add(cur_cell >= 0, cur_cell, cur_cnt, facc);
+  nav_wave_add(cur_cell >= 0, cur_cell, cur_cnt, facc);
 }
 
 // Finish: one thread per cell and frame.  acc != nullptr: hits = min(acc, 65535) is written; acc == nullptr: hits is read (the merge's
 // recomputation).  grid from hits and the frame's bins (jn_costmap.h).
 __global__ void __launch_bounds__(256) k_costmap_finish(CmDev s, int n, const uint32_t* __restrict__ acc, uint16_t* __restrict__ hits,
                                                         const double* __restrict__ bins, int8_t* __restrict__ grid) {
-  const int cells = s.cx * s.cy;
+  const int cells = s.c.cx * s.c.cy;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long long)n * cells) return;
   const int frame = (int)(t / cells), c = (int)(t - (long long)frame * cells);
@@ -156,16 +92,14 @@ __global__ void __launch_bounds__(256) k_costmap_finish(CmDev s, int n, const ui
   int8_t g = -1;
   if (h >= (uint32_t)s.min_hits) g = 100;
   else if (bins) {
-    const int iy = c / s.cx, ix = c - iy * s.cx;
-    const double xc = __dadd_rn(s.org_x, __dmul_rn(__dadd_rn((double)ix, 0.5), s.res));
-    const double yc = __dadd_rn(s.org_y, __dmul_rn(__dadd_rn((double)iy, 0.5), s.res));
-    const double th = atan2(yc, xc);
-    const double deg = __dmul_rn(th, 180.) / s.pi;                                                 // :254-263, as k_scan
-    const double kf = floor(__dmul_rn((double)s.bins, __dadd_rn(s.fov / 2., -deg)) / s.fov);
-    if (kf >= 0 && kf < (double)s.bins) {
-      const double b = bins[(size_t)frame * s.bins + (int)kf];
+    const int iy = c / s.c.cx, ix = c - iy * s.c.cx;
+    const double xc = __dadd_rn(s.c.org_x, __dmul_rn(__dadd_rn((double)ix, 0.5), s.c.res));
+    const double yc = __dadd_rn(s.c.org_y, __dmul_rn(__dadd_rn((double)iy, 0.5), s.c.res));
+    const double kf = nav_bin(s.g, atan2(yc, xc));
+    if (kf >= 0 && kf < (double)s.g.bins) {
+      const double b = bins[(size_t)frame * s.g.bins + (int)kf];
       const double r = sqrt(__dadd_rn(__dmul_rn(yc, yc), __dmul_rn(xc, xc)));
-      if (b < JN_SCAN_EMPTY - 1 && __dadd_rn(r, s.res) <= b) g = 0;
+      if (b < JN_SCAN_EMPTY - 1 && __dadd_rn(r, s.c.res) <= b) g = 0;
     }
   }
   grid[t] = g;
@@ -183,18 +117,7 @@ __global__ void __launch_bounds__(256) k_costmap_pack(long long count, uint16_t*
   }
 }
 
-CmDev cm_to_dev(const jn_scan_params& sp, const jn_costmap_params& cp) {
-  CmDev s;
-  for (int i = 0; i < 16; i++) s.Q[i] = sp.Q[i];
-  for (int i = 0; i < 9; i++) s.XR[i] = sp.XR[i];
-  for (int i = 0; i < 3; i++) s.XT[i] = sp.XT[i];
-  s.ox = sp.crop_offset_x; s.oy = sp.crop_offset_y;
-  s.gp_h = sp.gp_height_thresh; s.gp_tan = tan(sp.gp_angle_thresh); s.gp_dist = sp.gp_dist_thresh;
-  s.fov = sp.fov_deg; s.pi = sp.pi_approx; s.bins = sp.bins;
-  s.org_x = cp.origin_x; s.org_y = cp.origin_y; s.res = cp.resolution;
-  s.cx = cp.cells_x; s.cy = cp.cells_y; s.min_hits = cp.min_hits;
-  return s;
-}
+CmDev cm_to_dev(const jn_scan_params& sp, const jn_costmap_params& cp) { return CmDev{nav_geom(sp), nav_grid(cp), cp.min_hits}; }
 
 }  // namespace
 
@@ -233,15 +156,6 @@ void launch_costmap_pack(hipStream_t st, long long count, uint16_t* hits, double
 
 using namespace jnav;
 
-#define CM_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
-
 extern "C" {
 
 void jn_costmap_params_default(jn_costmap_params* cp) {
@@ -254,19 +168,12 @@ jn_status jn_obstacle_costmap(int32_t device, const jn_scan_params* sp, const jn
   if (!sp || !costmap_params_valid(cp) || !dDisp || !dHits || !dGrid || n < 1 || W < 1 || H < 1 || sp->bins < 1 || sp->bins > 1024 ||
       (!cp->from_cloud && !dLut))
     return JN_ERR_INVALID;
-  CM_TRY(hipSetDevice(device));
-  // grow-only scratch per device and calling thread, as the scan's: no hipMalloc / hipFree (a device-wide sync) per call
-  struct Scratch { uint32_t* p = nullptr; size_t cap = 0; int dev = -1; };
-  static thread_local Scratch sc;
-  const size_t need = costmap_scratch_bytes(*cp, n);
-  if (sc.dev != device || sc.cap < need) {
-    if (sc.p) { hipSetDevice(sc.dev); hipFree(sc.p); hipSetDevice(device); sc.p = nullptr; sc.cap = 0; }
-    CM_TRY(hipMalloc(reinterpret_cast<void**>(&sc.p), need));
-    sc.cap = need; sc.dev = device;
-  }
-  CM_TRY(launch_costmap(nullptr, *sp, *cp, n, dDisp, dLut, W, H, dBins, sc.p, dHits, dGrid));
-  CM_TRY(hipStreamSynchronize(nullptr));
-  CM_TRY(hipGetLastError());
+  HIP_TRY(hipSetDevice(device));
+  void* acc = nullptr;
+  HIP_TRY(thread_scratch(device, costmap_scratch_bytes(*cp, n), &acc));
+  HIP_TRY(launch_costmap(nullptr, *sp, *cp, n, dDisp, dLut, W, H, dBins, static_cast<uint32_t*>(acc), dHits, dGrid));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 

@@ -11,18 +11,12 @@
 // count a ballot's s_bcnt1 into a scalar.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <vector>
-#include "../../include/jn_ground.h"
+#include "nav_tail.h"
 
 namespace jnav {
 namespace {
-
-#define DEV static __device__ __forceinline__
-
-constexpr int kMaxQ = 16 * JN_GROUND_MAX_SIDE;
 
 // One hypothesis as the scoring passes read it (32 bytes: one s_load_dwordx8).  The test is  (u64)(A x + C q + B y + ept) <= t2  with
 // ept = E + T, t2 = 2 T, T = tol_q |C|.  VOID: A = B = C = 0, ept = 1, t2 = 0 — never true.
@@ -45,28 +39,9 @@ DEV uint32_t mix32(uint32_t x) {
   return x;
 }
 
-// q of one element; returns false for an invalid pixel
-template <int FMT> struct Elem;
-template <> struct Elem<JN_GROUND_F32> { typedef float T; };
-template <> struct Elem<JN_GROUND_I16> { typedef int16_t T; };
-template <> struct Elem<JN_GROUND_I16_SUB> { typedef int16_t T; };
-
-template <int FMT>
-DEV bool to_q(typename Elem<FMT>::T v, int minq, int& q) {
-  if (FMT == JN_GROUND_F32) {
-    const float d = (float)v;
-    const float t = rintf(__fmul_rn(16.f, d));
-    const bool ok = isfinite(d) && t >= (float)minq && t <= (float)kMaxQ;
-    q = ok ? (int)t : 0;
-    return ok;
-  }
-  q = FMT == JN_GROUND_I16 ? 16 * (int)v : (int)v;
-  return q >= minq && q <= kMaxQ;
-}
-
 // ---- sampling: one thread per (frame, hypothesis) ----
 template <int FMT>
-__global__ void __launch_bounds__(256) k_ground_sample(GrDev s, int n, const typename Elem<FMT>::T* __restrict__ disp, GrHyp* __restrict__ tab,
+__global__ void __launch_bounds__(256) k_ground_sample(GrDev s, int n, const typename DispElem<FMT>::T* __restrict__ disp, GrHyp* __restrict__ tab,
                                                         long long* __restrict__ hyps) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n * s.K) return;
@@ -80,7 +55,7 @@ __global__ void __launch_bounds__(256) k_ground_sample(GrDev s, int n, const typ
       const uint32_t h = mix32(s.seed ^ mix32(((((uint32_t)f * 1024u + (uint32_t)k) * 3u + (uint32_t)j) * 8u) + (uint32_t)a));
       const int x = s.x0 + (int)(((h & 0xffffu) * (uint32_t)rw) >> 16), y = s.y0 + (int)(((h >> 16) * (uint32_t)rh) >> 16);
       int q;
-      if (to_q<FMT>(disp[((long long)f * s.H + y) * s.W + x], s.minq, q)) { px[j] = x; py[j] = y; pq[j] = q; found = true; }
+      if (disp_to_q<FMT>(disp[((long long)f * s.H + y) * s.W + x], s.minq, q)) { px[j] = x; py[j] = y; pq[j] = q; found = true; }
     }
     ok = found;
   }
@@ -114,8 +89,8 @@ struct Run {
 // begin before roi_x0 or before the row; elements outside the region are masked, chunks that miss it are not loaded, and a chunk that would
 // cross the end of the array is read element by element.
 template <int FMT, int NCH>
-DEV void load_run(const GrDev& s, const typename Elem<FMT>::T* __restrict__ disp, int f, int y, int seg, int lane, int vec, Run<FMT, NCH>& r) {
-  typedef typename Elem<FMT>::T T;
+DEV void load_run(const GrDev& s, const typename DispElem<FMT>::T* __restrict__ disp, int f, int y, int seg, int lane, int vec, Run<FMT, NCH>& r) {
+  typedef typename DispElem<FMT>::T T;
   const long long row = ((long long)f * s.H + y) * s.W;
   const long long first = vec ? ((row + s.x0) & ~3ll) : row + s.x0;
 #pragma unroll
@@ -143,7 +118,7 @@ DEV void load_run(const GrDev& s, const typename Elem<FMT>::T* __restrict__ disp
 #pragma unroll
     for (int e = 0; e < 4; e++) {
       int q;
-      const bool ok = to_q<FMT>(v[e], s.minq, q) && touches && xb + e >= s.x0 && xb + e < s.x1;
+      const bool ok = disp_to_q<FMT>(v[e], s.minq, q) && touches && xb + e >= s.x0 && xb + e < s.x1;
       r.q[c][e] = ok ? q : 0;
       r.ok[c][e] = ok;
     }
@@ -161,7 +136,7 @@ DEV int in_loop(int v) {
 
 // ---- scoring: the hot path ----
 template <int FMT, int NCH>
-__global__ void __launch_bounds__(256) k_ground_score(GrDev s, const typename Elem<FMT>::T* __restrict__ disp, const GrHyp* __restrict__ tab,
+__global__ void __launch_bounds__(256) k_ground_score(GrDev s, const typename DispElem<FMT>::T* __restrict__ disp, const GrHyp* __restrict__ tab,
                                                        uint32_t* __restrict__ scores, int vec) {
   __shared__ uint32_t cnt[JN_GROUND_MAX_HYPOTHESES];
   const int f = blockIdx.y, lane = threadIdx.x & 63;
@@ -228,7 +203,7 @@ __global__ void __launch_bounds__(64) k_ground_pick(int K, const uint32_t* __res
 
 // ---- refit: the second pass, with the winner; eleven sums per frame ----
 template <int FMT, int NCH>
-__global__ void __launch_bounds__(256) k_ground_refit(GrDev s, const typename Elem<FMT>::T* __restrict__ disp, const GrHyp* __restrict__ tab,
+__global__ void __launch_bounds__(256) k_ground_refit(GrDev s, const typename DispElem<FMT>::T* __restrict__ disp, const GrHyp* __restrict__ tab,
                                                        const int32_t* __restrict__ best, unsigned long long* __restrict__ sums, int vec) {
   const int f = blockIdx.y, lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -345,7 +320,7 @@ int blocks_per_frame(const GrDev& s, int n) {
 }
 
 template <int FMT, int NCH>
-void launch_passes(hipStream_t st, GrDev s, int n, const typename Elem<FMT>::T* d, int vec, GrHyp* tab, uint32_t* scores, int32_t* best,
+void launch_passes(hipStream_t st, GrDev s, int n, const typename DispElem<FMT>::T* d, int vec, GrHyp* tab, uint32_t* scores, int32_t* best,
                    unsigned long long* sums) {
   const int rw = s.x1 - s.x0;
   s.segs = (rw + 3 + 256 * NCH - 1) / (256 * NCH);            // + 3: a run may begin up to three pixels left of the region
@@ -358,7 +333,7 @@ void launch_passes(hipStream_t st, GrDev s, int n, const typename Elem<FMT>::T* 
 template <int FMT>
 hipError_t launch_ground(hipStream_t st, const GrDev& s, int n, const void* disp, GrHyp* tab, long long* hyps, uint32_t* scores, int32_t* best,
                          unsigned long long* sums) {
-  typedef typename Elem<FMT>::T T;
+  typedef typename DispElem<FMT>::T T;
   const T* d = static_cast<const T*>(disp);
   // the clears on the SAME stream, as costmap.hip's
   hipError_t e = hipMemsetAsync(scores, 0, sizeof(uint32_t) * (size_t)n * s.K, st);
@@ -385,15 +360,6 @@ void mat3_mul(const double A[9], const double B[9], double C[9]) {
 
 using namespace jnav;
 
-#define GR_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
-
 extern "C" {
 
 void jn_ground_params_default(jn_ground_params* gp, int32_t W, int32_t H) {
@@ -409,7 +375,7 @@ jn_status jn_ground_estimate(int32_t device, const jn_scan_params* sp, const jn_
       (format != JN_GROUND_F32 && format != JN_GROUND_I16 && format != JN_GROUND_I16_SUB) || !ground_params_valid(gp, W, H) ||
       n > 65535 || !q_transpose_ok(sp, QT))
     return JN_ERR_INVALID;
-  GR_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   GrDev s;
   s.W = W; s.H = H; s.x0 = gp->roi_x0; s.y0 = gp->roi_y0; s.x1 = gp->roi_x1; s.y1 = gp->roi_y1; s.K = gp->hypotheses; s.minq = 16 * gp->min_disp;
   s.seed = gp->seed; s.tol = gp->tol_q;
@@ -418,31 +384,26 @@ jn_status jn_ground_estimate(int32_t device, const jn_scan_params* sp, const jn_
   const size_t K = (size_t)s.K;
   const size_t o_tab = 0, o_hyps = o_tab + align256(sizeof(GrHyp) * n * K), o_scores = o_hyps + align256(32 * n * K),
                o_best = o_scores + align256(4 * n * K), o_sums = o_best + align256(8 * (size_t)n), need = o_sums + align256(88 * (size_t)n);
-  // grow-only scratch per device and calling thread, as the costmap's: no hipMalloc / hipFree (a device-wide sync) per call
-  struct Scratch { char* p = nullptr; size_t cap = 0; int dev = -1; };
-  static thread_local Scratch sc;
-  if (sc.dev != device || sc.cap < need) {
-    if (sc.p) { (void)hipSetDevice(sc.dev); (void)hipFree(sc.p); (void)hipSetDevice(device); sc.p = nullptr; sc.cap = 0; }
-    GR_TRY(hipMalloc(reinterpret_cast<void**>(&sc.p), need));
-    sc.cap = need; sc.dev = device;
-  }
-  GrHyp* tab = reinterpret_cast<GrHyp*>(sc.p + o_tab);
-  long long* dh = reinterpret_cast<long long*>(sc.p + o_hyps);
-  uint32_t* dsc = reinterpret_cast<uint32_t*>(sc.p + o_scores);
-  int32_t* dbest = reinterpret_cast<int32_t*>(sc.p + o_best);
-  unsigned long long* dsums = reinterpret_cast<unsigned long long*>(sc.p + o_sums);
+  void* scratch = nullptr;
+  HIP_TRY(thread_scratch(device, need, &scratch));
+  char* const p = static_cast<char*>(scratch);
+  GrHyp* tab = reinterpret_cast<GrHyp*>(p + o_tab);
+  long long* dh = reinterpret_cast<long long*>(p + o_hyps);
+  uint32_t* dsc = reinterpret_cast<uint32_t*>(p + o_scores);
+  int32_t* dbest = reinterpret_cast<int32_t*>(p + o_best);
+  unsigned long long* dsums = reinterpret_cast<unsigned long long*>(p + o_sums);
   const hipError_t launched = format == JN_GROUND_F32   ? launch_ground<JN_GROUND_F32>(nullptr, s, n, dDisp, tab, dh, dsc, dbest, dsums)
                              : format == JN_GROUND_I16 ? launch_ground<JN_GROUND_I16>(nullptr, s, n, dDisp, tab, dh, dsc, dbest, dsums)
                                                        : launch_ground<JN_GROUND_I16_SUB>(nullptr, s, n, dDisp, tab, dh, dsc, dbest, dsums);
-  GR_TRY(launched);                                           // (the macro prints its argument: no JN_ names in it, tests/test_abi.py counts them)
-  GR_TRY(hipStreamSynchronize(nullptr));
-  GR_TRY(hipGetLastError());
+  HIP_TRY(launched);                                           // (the macro prints its argument: no JN_ names in it, tests/test_abi.py counts them)
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   std::vector<int32_t> hb(2 * (size_t)n);
   std::vector<int64_t> hs(11 * (size_t)n);
-  GR_TRY(hipMemcpy(hb.data(), dbest, 8 * (size_t)n, hipMemcpyDeviceToHost));
-  GR_TRY(hipMemcpy(hs.data(), dsums, 88 * (size_t)n, hipMemcpyDeviceToHost));
-  if (scores) GR_TRY(hipMemcpy(scores, dsc, 4 * n * K, hipMemcpyDeviceToHost));
-  if (hyps) GR_TRY(hipMemcpy(hyps, dh, 32 * n * K, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hb.data(), dbest, 8 * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hs.data(), dsums, 88 * (size_t)n, hipMemcpyDeviceToHost));
+  if (scores) HIP_TRY(hipMemcpy(scores, dsc, 4 * n * K, hipMemcpyDeviceToHost));
+  if (hyps) HIP_TRY(hipMemcpy(hyps, dh, 32 * n * K, hipMemcpyDeviceToHost));
   for (int f = 0; f < n; f++) {
     solve_plane(sp, gp->min_inliers, gp->min_inlier_frac, &hs[11 * (size_t)f], hs[11 * (size_t)f + 10], &out[f]);
     out[f].best = hb[2 * f];

@@ -14,6 +14,7 @@
 #include "../../include/jn_stereo.h"
 #include "hooks.h"
 #include "kernels.h"
+#include "nav_tail.h"
 #include "host_stage.h"
 #include "pool.h"
 
@@ -37,21 +38,7 @@
 
 using namespace jnav;
 
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
-
 namespace {
-
-// The obstacle costmap as part of a slot's scan tail (jn_elas_attach_costmap, include/jn_costmap.h)
-struct CostmapTail { bool on = false; jn_costmap_params cp = {}; uint16_t* hits = nullptr; int8_t* grid = nullptr; };
-// The sub-pixel tail of a slot's scan batch (jn_elas_attach_subpix, include/jn_subpix.h); has_cp: the costmap with the scan
-struct SubpixTail { bool on = false, has_cp = false; jn_costmap_params cp = {}; double* bins = nullptr; double* meta = nullptr; uint16_t* hits = nullptr; int8_t* grid = nullptr; };
 
 struct Job {
   int n = 0; const uint8_t* dI1 = nullptr; const uint8_t* dI2 = nullptr; int pitch = 0; int64_t stride = 0;
@@ -62,8 +49,7 @@ struct Job {
   bool host = false; const uint8_t* hI1 = nullptr; const uint8_t* hI2 = nullptr; float* hD1 = nullptr; float* hD2 = nullptr;
   // optional tail of the node on the same stream (jn_elas_submit_scan): u8 map + LUT scan of D1
   bool scan = false; jn_scan_params sp = {}; const uint8_t* dLut = nullptr; uint8_t* dDispU8 = nullptr; double* dBins = nullptr; double* dMeta = nullptr;
-  CostmapTail cm;                                             // what was attached to the slot when the scan batch was submitted
-  SubpixTail sx;
+  NavTails tails;                                             // what was attached to the slot when the scan batch was submitted
 };
 
 enum { EV_BEGIN, EV_DESC, EV_SUPPORT, EV_D2H, EV_H2D0, EV_H2D, EV_RASTER, EV_DENSE, EV_LR, EV_SPECKLE, EV_GAP, EV_AM, EV_END, EV_COUNT };
@@ -83,8 +69,7 @@ struct Slot {
   float* tmp = nullptr; int32_t* label = nullptr; int32_t* size = nullptr;
   uint32_t* mark = nullptr; uint32_t* gridbits = nullptr; TriRec* recs = nullptr;
   unsigned long long* scan_scratch = nullptr;                 // extrema of the scan tail, 4 per frame
-  CostmapTail cm; uint32_t* cm_acc = nullptr; size_t cm_acc_bytes = 0;   // attached costmap and its accumulation grid [max_batch][cells] u32 (allocated by the attach call)
-  SubpixTail sx; void* sx_scratch = nullptr; size_t sx_bytes = 0;        // attached sub-pixel tail and its scratch (subpix_scratch_bytes; allocated by the attach call)
+  NavTails tails;                                             // attached costmap and sub-pixel tail, with their scratch (allocated by the attach calls)
   uint8_t* st_img = nullptr; float* st_D = nullptr;           // device staging of jn_elas_submit_host: [2][max_batch] images / maps, allocated on first use
   std::vector<FrameScratch> scratch;
   std::vector<HostWorker::SideState> sides;                  // [2 * max_batch]: per frame side, for the phased (parallel) triangulation
@@ -409,12 +394,9 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
     }
     if (j.scan)                                            // the node's tail: depth map + obstacle scan of whatever D1 now holds
       launch_scan(st, j.sp, n, j.dD1, j.dDispU8, j.dLut, dp.W, dp.H, j.dBins, j.dMeta, s.scan_scratch, j.merge ? s.d_flat : nullptr);
-    if (j.scan && j.cm.on)                                 // the obstacle costmap of the map and the bins the scan has just written, same stream
-      HIP_TRY(launch_costmap(st, j.sp, j.cm.cp, n, j.dDispU8, j.dLut, dp.W, dp.H, j.dBins, s.cm_acc, j.cm.hits, j.cm.grid));
-    if (j.scan && j.sx.on) {                               // the sub-pixel tail: scan (and costmap) of the float map itself, behind everything above
-      jn_subpix_params fp;
-      jn_subpix_params_default(&fp, JN_DISP_F32);
-      launch_subpix(st, j.sp, j.sx.has_cp ? &j.sx.cp : nullptr, fp, n, j.dD1, dp.W, dp.H, j.sx.bins, j.sx.meta, j.sx.hits, j.sx.grid, s.sx_scratch);
+    if (j.scan) {                                          // the attached tails: the costmap of the map and the bins the scan has just written, the sub-pixel tail of the float map
+      const int native = JN_DISP_F32;
+      HIP_TRY(j.tails.launch(st, j.sp, n, j.dDispU8, j.dLut, j.dBins, j.dD1, native, dp.W, dp.H));
     }
     HIP_TRY(hipEventRecord(s.ev[EV_END], st));
     return JN_OK;
@@ -927,7 +909,7 @@ void jn_elas_destroy(jn_elas* h) {
   hipSetDevice(h->device);
   for (auto& s : h->slots) {
     hipFree(s->desc); hipFree(s->planes); hipFree(s->d_can); hipFree(s->info); hipFree(s->payload);
-    hipFree(s->bin_count); hipFree(s->bin_list); hipFree(s->raw); hipFree(s->tmp); hipFree(s->label); hipFree(s->size); hipFree(s->scan_scratch); hipFree(s->cm_acc); hipFree(s->sx_scratch); hipFree(s->d_flat); hipFree(s->st_img); hipFree(s->st_D); hipFree(s->arr_scratch);
+    hipFree(s->bin_count); hipFree(s->bin_list); hipFree(s->raw); hipFree(s->tmp); hipFree(s->label); hipFree(s->size); hipFree(s->scan_scratch); s->tails.release(); hipFree(s->d_flat); hipFree(s->st_img); hipFree(s->st_D); hipFree(s->arr_scratch);
     hipFree(s->mark); hipFree(s->gridbits); hipFree(s->recs);
     hipHostFree(s->h_can); hipHostFree(s->h_info); hipHostFree(s->h_payload); hipHostFree(s->h_list); hipHostFree(s->h_cnt); hipHostFree(s->h_arr); hipHostFree(s->h_arr_ok);
     for (int e = 0; e < EV_COUNT; e++) if (s->ev[e]) hipEventDestroy(s->ev[e]);
@@ -997,8 +979,7 @@ jn_status jn_elas_submit_scan(jn_elas* h, int32_t slot, int32_t n, const uint8_t
     s.cv.wait(l, [&] { return !s.busy; });
     s.job = Job{n, dI1, dI2, pitch, image_stride, dD1, dD2, status};
     s.job.scan = true; s.job.sp = *sp; s.job.dLut = dLut; s.job.dDispU8 = dDispU8; s.job.dBins = dBins; s.job.dMeta = dMeta;
-    s.job.cm = s.cm;
-    s.job.sx = s.sx;
+    s.job.tails = s.tails;
     {
       std::lock_guard<std::mutex> g(h->merge_m);             // the submitting thread numbers the batches: same order on every rank
       if (h->comm) { s.job.merge = true; s.job.seq = h->submit_seq++; }
@@ -1011,41 +992,18 @@ jn_status jn_elas_submit_scan(jn_elas* h, int32_t slot, int32_t n, const uint8_t
 
 jn_status jn_elas_attach_costmap(jn_elas* h, int32_t slot, const jn_costmap_params* cp, uint16_t* dHits, int8_t* dGrid) {
   if (!h || slot < 0 || slot >= (int)h->slots.size()) return JN_ERR_INVALID;
-  if (cp && (!costmap_params_valid(cp) || !dHits || !dGrid)) return JN_ERR_INVALID;
   Slot& s = *h->slots[slot];
   std::unique_lock<std::mutex> l(s.m);
   s.cv.wait(l, [&] { return !s.busy; });                    // no batch in flight on the slot
-  if (!cp) { s.cm = CostmapTail(); return JN_OK; }
-  const size_t need = costmap_scratch_bytes(*cp, h->max_batch);
-  if (need > s.cm_acc_bytes) {                              // grow-only; the slot is idle, nothing reads the old grid
-    HIP_TRY(hipSetDevice(h->device));
-    if (s.cm_acc) { hipFree(s.cm_acc); s.cm_acc = nullptr; s.cm_acc_bytes = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.cm_acc), need));
-    s.cm_acc_bytes = need;
-  }
-  s.cm.on = true; s.cm.cp = *cp; s.cm.hits = dHits; s.cm.grid = dGrid;
-  return JN_OK;
+  return s.tails.attach_costmap(h->device, h->max_batch, cp, dHits, dGrid);
 }
 
 jn_status jn_elas_attach_subpix(jn_elas* h, int32_t slot, const jn_costmap_params* cp, double* dBins, double* dMeta, uint16_t* dHits, int8_t* dGrid) {
   if (!h || slot < 0 || slot >= (int)h->slots.size()) return JN_ERR_INVALID;
-  const bool detach = !cp && !dBins && !dMeta && !dHits && !dGrid;
-  if (!detach && (!dBins || !dMeta || (cp ? (!costmap_params_valid(cp) || !dHits || !dGrid) : (dHits || dGrid)))) return JN_ERR_INVALID;
   Slot& s = *h->slots[slot];
   std::unique_lock<std::mutex> l(s.m);
   s.cv.wait(l, [&] { return !s.busy; });                    // no batch in flight on the slot
-  if (detach) { s.sx = SubpixTail(); return JN_OK; }
-  const size_t need = subpix_scratch_bytes(cp, h->max_batch);
-  if (need > s.sx_bytes) {                                  // grow-only; the slot is idle, nothing reads the old scratch
-    HIP_TRY(hipSetDevice(h->device));
-    if (s.sx_scratch) { hipFree(s.sx_scratch); s.sx_scratch = nullptr; s.sx_bytes = 0; }
-    HIP_TRY(hipMalloc(&s.sx_scratch, need));
-    s.sx_bytes = need;
-  }
-  s.sx = SubpixTail();
-  s.sx.on = true; s.sx.has_cp = cp != nullptr; if (cp) s.sx.cp = *cp;
-  s.sx.bins = dBins; s.sx.meta = dMeta; s.sx.hits = dHits; s.sx.grid = dGrid;
-  return JN_OK;
+  return s.tails.attach_subpix(h->device, h->max_batch, cp, dBins, dMeta, dHits, dGrid);
 }
 
 jn_status jn_elas_set_comm(jn_elas* h, jn_comm* c) {
@@ -1188,16 +1146,9 @@ static jn_status scan_common(int32_t device, const jn_scan_params* sp, int32_t n
                              const uint8_t* dLut, int32_t W, int32_t H, double* dBins, double* dMeta) {
   if (!sp || !dDisp || !dBins || !dMeta || n < 1 || sp->bins < 1 || sp->bins > 1024) return JN_ERR_INVALID;
   HIP_TRY(hipSetDevice(device));
-  // grow-only scratch per device and calling thread: no hipMalloc/hipFree (a device-wide sync) per call
-  struct Scratch { unsigned long long* p = nullptr; int cap = 0; int dev = -1; };
-  static thread_local Scratch sc;
-  if (sc.dev != device || sc.cap < n) {
-    if (sc.p) { hipSetDevice(sc.dev); hipFree(sc.p); hipSetDevice(device); sc.p = nullptr; }
-    const int cap = n > 64 ? n : 64;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sc.p), sizeof(unsigned long long) * 4 * cap));
-    sc.cap = cap; sc.dev = device;
-  }
-  launch_scan(nullptr, *sp, n, dD, dDisp, dLut, W, H, dBins, dMeta, sc.p);
+  void* extrema = nullptr;                                    // [n][4] uint64
+  HIP_TRY(thread_scratch(device, sizeof(unsigned long long) * 4 * (size_t)n, &extrema));
+  launch_scan(nullptr, *sp, n, dD, dDisp, dLut, W, H, dBins, dMeta, static_cast<unsigned long long*>(extrema));
   HIP_TRY(hipStreamSynchronize(nullptr));
   HIP_TRY(hipGetLastError());
   return JN_OK;
@@ -1231,13 +1182,12 @@ jn_status jn_point_cloud(int32_t device, const jn_scan_params* sp, const uint8_t
                          int64_t* count) {
   if (!sp || !dDisp || !dXyz || !count || W < 1 || H < 1) return JN_ERR_INVALID;
   HIP_TRY(hipSetDevice(device));
-  long long* cols = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cols), sizeof(long long) * (W + 1)));
+  void* scratch = nullptr;
+  HIP_TRY(thread_scratch(device, sizeof(long long) * ((size_t)W + 1), &scratch));
+  long long* cols = static_cast<long long*>(scratch);
   launch_point_cloud(nullptr, *sp, dDisp, W, H, dXyz, cols);
   long long total = 0;
-  hipError_t e = hipMemcpy(&total, cols + W, sizeof(long long), hipMemcpyDeviceToHost);
-  hipFree(cols);
-  HIP_TRY(e);
+  HIP_TRY(hipMemcpy(&total, cols + W, sizeof(long long), hipMemcpyDeviceToHost));
   HIP_TRY(hipGetLastError());
   *count = total;
   return JN_OK;

@@ -15,7 +15,7 @@
 #include "../../include/jn_costmap.h"
 #include "../../include/jn_subpix.h"
 #include "sgm_sweep.h"
-#include "kernels.h"            // launch_scan, launch_costmap, launch_subpix: the node's tails on a slot's stream (jn_sgm_submit_scan)
+#include "nav_tail.h"           // kernels.h's launch_scan, and NavTails: the node's tails on a slot's stream (jn_sgm_submit_scan)
 
 namespace {
 
@@ -48,24 +48,9 @@ struct jn_sgm {
   Extra extra[kSgmSlots - 1];
   unsigned long long* scan_scratch[kSgmSlots] = {};   // [max_batch][4] per slot, the scan tail's extrema
   bool pending[kSgmSlots] = {};
-  // the obstacle costmap as part of a slot's scan tail (jn_sgm_attach_costmap, include/jn_costmap.h): acc [max_batch][cells] u32, allocated by the attach call
-  struct Costmap { bool on = false; jn_costmap_params cp = {}; uint16_t* hits = nullptr; int8_t* grid = nullptr; uint32_t* acc = nullptr; size_t acc_bytes = 0; };
-  Costmap costmap[kSgmSlots];
-  // the sub-pixel tail of a slot's scan batch (jn_sgm_attach_subpix, include/jn_subpix.h); scratch allocated by the attach call
-  struct Subpix { bool on = false, has_cp = false; jn_costmap_params cp = {}; double* bins = nullptr; double* meta = nullptr; uint16_t* hits = nullptr; int8_t* grid = nullptr;
-                  void* scratch = nullptr; size_t scratch_bytes = 0; };
-  Subpix subpix[kSgmSlots];
+  jnav::NavTails tails[kSgmSlots];    // what jn_sgm_attach_costmap / jn_sgm_attach_subpix attached to each slot's scan batches
   static_assert(kSgmSlots == sizeof(ev_end) / sizeof(ev_end[0]), "one end event per slot");
 };
-
-#define SGM_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
 
 extern "C" {
 
@@ -85,8 +70,7 @@ void jn_sgm_destroy(jn_sgm* h) {
     if (x.stream && !x.shared) hipStreamDestroy(x.stream);
   }
   for (auto& q : h->scan_scratch) hipFree(q);
-  for (auto& c : h->costmap) hipFree(c.acc);
-  for (auto& x : h->subpix) hipFree(x.scratch);
+  for (auto& t : h->tails) t.release();
   jnav_sgm::sweep_release(h->sb);
   hipFree(h->sb.gm); hipFree(h->sb.volF); hipFree(h->sb.volH0); hipFree(h->sb.volH1); hipFree(h->sb.gx); hipFree(h->sb.flags); hipFree(h->sb.minr); hipFree(h->sb.dl);
   for (auto& e : h->ev) if (e) hipEventDestroy(e);
@@ -104,7 +88,7 @@ jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t ma
     return JN_ERR_UNSUPPORTED;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
-  SGM_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   jn_sgm* h = new jn_sgm();
   h->p = *p; h->W = W; h->H = H; h->max_batch = max_batch; h->device = device;
 #define SGM_CREATE_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { fprintf(stderr, "libjn_stereo: %s failed: %s\n", #expr, hipGetErrorString(e__)); jn_sgm_destroy(h); return JN_ERR_NO_DEVICE; } } while (0)
@@ -135,11 +119,11 @@ jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t ma
 jn_status jn_sgm_process_batch(jn_sgm* h, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride, int16_t* dDisp) {
   if (!h || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dDisp || pitch < h->W) return JN_ERR_INVALID;
   if (h->pending[0]) return JN_ERR_INVALID;                     // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
-  SGM_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
-  SGM_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, h->sb, h->ev, true));
-  SGM_TRY(hipStreamSynchronize(st));
-  SGM_TRY(hipGetLastError());
+  HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, h->sb, h->ev, true));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
   hipEventElapsedTime(&h->times.prefilter, h->ev[0], h->ev[1]);
   hipEventElapsedTime(&h->times.paths, h->ev[1], h->ev[2]);
   hipEventElapsedTime(&h->times.wta, h->ev[2], h->ev[3]);
@@ -153,16 +137,16 @@ static jn_status sgm_ensure_slot(jn_sgm* h, int slot) {
   jn_sgm::Extra& x = h->extra[slot - 1];
   if (x.ready) return JN_OK;
   const jnav_sgm::SweepSizes& z = h->sizes;
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gm), z.gm));
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volF), z.vol * (h->sw.wide ? 2 : 1)));
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH0), z.vol));
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH1), z.vol));
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gx), z.gx));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gm), z.gm));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volF), z.vol * (h->sw.wide ? 2 : 1)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH0), z.vol));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH1), z.vol));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gx), z.gx));
   x.sb.gx_bytes = z.gx;
   x.sb.epoch = h->sb.epoch;                                     // (tests start it next to the tag's wrap-around)
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.flags), z.flags));
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.minr), z.minr));
-  SGM_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.dl), z.dl));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.flags), z.flags));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.minr), z.minr));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.dl), z.dl));
   {
     static const int share = getenv("JN_SGM_STREAMS") ? atoi(getenv("JN_SGM_STREAMS")) : 0;     // experiment: slot s queues on the stream of slot s % share
     if (share > 0 && slot >= share) {
@@ -170,10 +154,10 @@ static jn_status sgm_ensure_slot(jn_sgm* h, int slot) {
       const jn_status el = sgm_ensure_slot(h, lower);
       if (el != JN_OK) return el;
       x.stream = lower == 0 ? h->stream : h->extra[lower - 1].stream; x.shared = true;
-    } else SGM_TRY(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
+    } else HIP_TRY(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
   }
-  SGM_TRY(hipMemsetAsync(x.sb.gx, 0, x.sb.gx_bytes, x.stream)); // ahead of the slot's first sweep in stream order (see jn_sgm_create)
-  for (auto& e : x.ev) SGM_TRY(hipEventCreate(&e));
+  HIP_TRY(hipMemsetAsync(x.sb.gx, 0, x.sb.gx_bytes, x.stream)); // ahead of the slot's first sweep in stream order (see jn_sgm_create)
+  for (auto& e : x.ev) HIP_TRY(hipEventCreate(&e));
   x.ready = true;
   return JN_OK;
 }
@@ -183,10 +167,10 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dDisp || pitch < h->W) return JN_ERR_INVALID;
   if (sp && (!dLut || !dDispU8 || !dBins || !dMeta || sp->bins < 1 || sp->bins > 1024)) return JN_ERR_INVALID;
   if (h->pending[slot]) return JN_ERR_INVALID;                  // one batch per slot: jn_sgm_wait first
-  SGM_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   const jn_status es = sgm_ensure_slot(h, slot);
   if (es != JN_OK) return es;
-  if (sp && !h->scan_scratch[slot]) SGM_TRY(hipMalloc(reinterpret_cast<void**>(&h->scan_scratch[slot]), sizeof(unsigned long long) * 4 * h->max_batch));
+  if (sp && !h->scan_scratch[slot]) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->scan_scratch[slot]), sizeof(unsigned long long) * 4 * h->max_batch));
   jnav_sgm::SweepBuffers& sb = slot == 0 ? h->sb : h->extra[slot - 1].sb;
   hipStream_t st = slot == 0 ? h->stream : h->extra[slot - 1].stream;
   hipEvent_t* ev = slot == 0 ? h->ev : h->extra[slot - 1].ev;
@@ -194,7 +178,7 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
   // (JN_SGM_TAIL=3: the three kernels k_sw_lr, k_sgm_to_u8, k_scan one after the other, for A/B).
   static const bool fused_tail = !(getenv("JN_SGM_TAIL") && atoi(getenv("JN_SGM_TAIL")) == 3);
   const bool fuse = sp && fused_tail;
-  SGM_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, sb, ev, false, !fuse));
+  HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, sb, ev, false, !fuse));
   if (fuse) {
     jnav::SgmWinners w;
     w.dl = sb.dl; w.minr = sb.minr; w.disp = dDisp; w.lr = h->sw.lr; w.subpixel = h->sw.subpixel;
@@ -204,69 +188,39 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
     hipLaunchKernelGGL(k_sgm_to_u8, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, dDisp, h->p.subpixel ? 1 : 0, dDispU8, px);
     jnav::launch_scan(st, *sp, n, nullptr, dDispU8, dLut, h->W, h->H, dBins, dMeta, h->scan_scratch[slot]);
   }
-  if (sp && h->costmap[slot].on) {                              // the obstacle costmap of the map and the bins the tail has just written, same stream
-    const jn_sgm::Costmap& c = h->costmap[slot];
-    SGM_TRY(jnav::launch_costmap(st, *sp, c.cp, n, dDispU8, dLut, h->W, h->H, dBins, c.acc, c.hits, c.grid));
-  }
-  if (sp && h->subpix[slot].on) {                               // the sub-pixel tail, from the int16 map: behind the tail kernel that writes it (the fused k_scan)
-    const jn_sgm::Subpix& x = h->subpix[slot];
-    jn_subpix_params fp;
-    jn_subpix_params_default(&fp, h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16);
-    jnav::launch_subpix(st, *sp, x.has_cp ? &x.cp : nullptr, fp, n, dDisp, h->W, h->H, x.bins, x.meta, x.hits, x.grid, x.scratch);
+  if (sp) {                                                     // the attached tails: the costmap of the mono8 map and the bins just written, the sub-pixel tail of the int16 map
+    const int native = h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16;
+    HIP_TRY(h->tails[slot].launch(st, *sp, n, dDispU8, dLut, dBins, dDisp, native, h->W, h->H));
   }
   // the batch's end: behind the scan tail, not behind the sweeps (ev[3] stays the end of the winner-takes-all timing)
-  if (!h->ev_end[slot]) SGM_TRY(hipEventCreateWithFlags(&h->ev_end[slot], hipEventDisableTiming));
-  SGM_TRY(hipEventRecord(h->ev_end[slot], st));
-  SGM_TRY(hipGetLastError());
+  if (!h->ev_end[slot]) HIP_TRY(hipEventCreateWithFlags(&h->ev_end[slot], hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->ev_end[slot], st));
+  HIP_TRY(hipGetLastError());
   h->pending[slot] = true;
   return JN_OK;
 }
 
 jn_status jn_sgm_attach_costmap(jn_sgm* h, int32_t slot, const jn_costmap_params* cp, uint16_t* dHits, int8_t* dGrid) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
-  if (cp && (!jnav::costmap_params_valid(cp) || !dHits || !dGrid)) return JN_ERR_INVALID;
   if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
-  jn_sgm::Costmap& c = h->costmap[slot];
-  if (!cp) { c.on = false; c.hits = nullptr; c.grid = nullptr; return JN_OK; }
-  const size_t need = jnav::costmap_scratch_bytes(*cp, h->max_batch);
-  if (need > c.acc_bytes) {                                     // grow-only; the slot is idle, nothing reads the old grid
-    SGM_TRY(hipSetDevice(h->device));
-    if (c.acc) { hipFree(c.acc); c.acc = nullptr; c.acc_bytes = 0; }
-    SGM_TRY(hipMalloc(reinterpret_cast<void**>(&c.acc), need));
-    c.acc_bytes = need;
-  }
-  c.on = true; c.cp = *cp; c.hits = dHits; c.grid = dGrid;
-  return JN_OK;
+  return h->tails[slot].attach_costmap(h->device, h->max_batch, cp, dHits, dGrid);
 }
 
 jn_status jn_sgm_attach_subpix(jn_sgm* h, int32_t slot, const jn_costmap_params* cp, double* dBins, double* dMeta, uint16_t* dHits, int8_t* dGrid) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
-  const bool detach = !cp && !dBins && !dMeta && !dHits && !dGrid;
-  if (!detach && (!dBins || !dMeta || (cp ? (!jnav::costmap_params_valid(cp) || !dHits || !dGrid) : (dHits || dGrid)))) return JN_ERR_INVALID;
   if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
-  jn_sgm::Subpix& x = h->subpix[slot];
-  if (detach) { x.on = false; x.has_cp = false; x.bins = x.meta = nullptr; x.hits = nullptr; x.grid = nullptr; return JN_OK; }
-  const size_t need = jnav::subpix_scratch_bytes(cp, h->max_batch);
-  if (need > x.scratch_bytes) {                                 // grow-only; the slot is idle, nothing reads the old scratch
-    SGM_TRY(hipSetDevice(h->device));
-    if (x.scratch) { hipFree(x.scratch); x.scratch = nullptr; x.scratch_bytes = 0; }
-    SGM_TRY(hipMalloc(&x.scratch, need));
-    x.scratch_bytes = need;
-  }
-  x.on = true; x.has_cp = cp != nullptr; if (cp) x.cp = *cp;
-  x.bins = dBins; x.meta = dMeta; x.hits = dHits; x.grid = dGrid;
-  return JN_OK;
+  return h->tails[slot].attach_subpix(h->device, h->max_batch, cp, dBins, dMeta, dHits, dGrid);
 }
 
 jn_status jn_sgm_wait(jn_sgm* h, int32_t slot) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
   if (!h->pending[slot]) return JN_OK;
-  SGM_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipEvent_t* ev = slot == 0 ? h->ev : h->extra[slot - 1].ev;
   jn_sgm_times& t = slot == 0 ? h->times : h->extra[slot - 1].times;
   h->pending[slot] = false;
-  SGM_TRY(hipEventSynchronize(h->ev_end[slot]));                // the slot's own end, scan tail included (its stream may carry a later slot's batch)
-  SGM_TRY(hipGetLastError());
+  HIP_TRY(hipEventSynchronize(h->ev_end[slot]));                // the slot's own end, scan tail included (its stream may carry a later slot's batch)
+  HIP_TRY(hipGetLastError());
   hipEventElapsedTime(&t.prefilter, ev[0], ev[1]);
   hipEventElapsedTime(&t.paths, ev[1], ev[2]);
   hipEventElapsedTime(&t.wta, ev[2], ev[3]);
@@ -293,10 +247,10 @@ jn_status jn_sgm_last_times(jn_sgm* h, jn_sgm_times* out) {
 
 jn_status jn_sgm_disparity_to_u8(int32_t device, const int16_t* dDisp, int32_t subpixel, uint8_t* dOut, int64_t n) {
   if (!dDisp || !dOut || n < 0) return JN_ERR_INVALID;
-  SGM_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   if (n) hipLaunchKernelGGL(k_sgm_to_u8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dDisp, subpixel ? 1 : 0, dOut, (long long)n);
-  SGM_TRY(hipStreamSynchronize(nullptr));
-  SGM_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 

@@ -3,109 +3,21 @@
 //
 // No reference counterpart; the definition is in jn_subpix.h, its scalar restatement (the checker) in tests/subpix_def.py.  The anchor
 // of that header — bit-identity with jn_obstacle_scan_cloud, jn_obstacle_costmap(from_cloud = 1) and jn_point_cloud on integer maps —
-// holds because every double operation below is the operation of kernels.hip's k_scan<true> / costmap.hip's accumulate on the same
-// operands in the same order: the reprojection is RESTATED a third time (kernels.hip is pinned by the evidence set's manifest and exports
-// nothing; costmap.hip's copy takes an int disparity), the grid classification is costmap.hip's own finish kernel.
+// holds because the reprojection, the ground model, the cell and the bin of a point are nav_tail.h's own functions, the ones costmap.hip
+// calls (kernels.hip's k_scan<true> holds the same text, see nav_tail.h), and the grid classification is costmap.hip's own finish kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include "kernels.h"
+#include "nav_tail.h"
 
 namespace jnav {
 namespace {
 
-#define DEV static __device__ __forceinline__
-
-constexpr int kMaxQ = 16 * JN_GROUND_MAX_SIDE;
-
 struct SpxDev {
-  double Q[16], XR[9], XT[3];
-  int ox, oy;
-  double gp_h, gp_tan, gp_dist, fov, pi;
-  int bins, min_q;
-  double org_x, org_y, res;
-  int cx, cy;
+  NavGeom g;
+  NavGrid c;
+  int min_q;
 };
-
-template <int FMT> struct Elem { using T = int16_t; };
-template <> struct Elem<JN_DISP_F32> { using T = float; };
-
-// jn_subpix.h "q" and "valid" (jn_ground.h's rule, ground.hip's to_q)
-template <int FMT>
-DEV bool spx_to_q(typename Elem<FMT>::T v, int min_q, int& q) {
-  if constexpr (FMT == JN_DISP_F32) {
-    const float t = rintf(__fmul_rn(16.f, v));
-    const bool ok = isfinite(v) && t >= (float)min_q && t <= (float)kMaxQ;
-    q = ok ? (int)t : 0;
-    return ok;
-  } else {
-    q = FMT == JN_DISP_I16 ? 16 * (int)v : (int)v;
-    return q >= min_q && q <= kMaxQ;
-  }
-}
-
-// pos = Q*[i+ox, j+oy, q/16, 1]; cam = pos.xyz/pos.w; robot = XR*cam + XT — kernels.hip's reproject() with V2 = q / 16.0 (exact)
-DEV bool spx_reproject(const SpxDev& s, int i, int j, int q, double& X, double& Y, double& Z) {
-  const double V0 = (double)(i + s.ox), V1 = (double)(j + s.oy), V2 = __dmul_rn((double)q, 0.0625);
-  double pos[4];
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    double a = __dmul_rn(s.Q[4 * r], V0);
-    a = __dadd_rn(a, __dmul_rn(s.Q[4 * r + 1], V1));
-    a = __dadd_rn(a, __dmul_rn(s.Q[4 * r + 2], V2));
-    a = __dadd_rn(a, s.Q[4 * r + 3]);
-    pos[r] = a;
-  }
-  if (pos[3] == 0.0) return false;
-  const double cx = pos[0] / pos[3], cy = pos[1] / pos[3], cz = pos[2] / pos[3];
-  double o[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    double a = __dmul_rn(s.XR[3 * r], cx);
-    a = __dadd_rn(a, __dmul_rn(s.XR[3 * r + 1], cy));
-    a = __dadd_rn(a, __dmul_rn(s.XR[3 * r + 2], cz));
-    o[r] = __dadd_rn(a, s.XT[r]);
-  }
-  X = o[0]; Y = o[1]; Z = o[2];
-  return true;
-}
-DEV bool spx_is_ground(const SpxDev& s, double X, double Z) {      // point_cloud.cpp:128-137 — kernels.hip's is_ground()
-  if (X < s.gp_dist) return Z < s.gp_h;
-  return Z < __dadd_rn(s.gp_h, __dmul_rn(s.gp_tan, X - s.gp_dist));
-}
-
-// order-preserving map double -> uint64 so that integer atomics implement min / max of doubles of either sign (kernels.hip's enc / dec)
-DEV unsigned long long spx_enc(double x) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-DEV double spx_dec(unsigned long long k) {
-  const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
-// costmap.hip's cm_wave_add: adds cnt to acc[cell] for every lane with `have`, the first kCombine distinct cells of the wave summed across
-// it and added once each by their first lane, the rest lane by lane.  Called by the whole wave (convergent).
-constexpr int kCombine = 4;
-DEV void spx_wave_add(bool have, int cell, uint32_t cnt, uint32_t* __restrict__ acc) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll 1
-  for (int it = 0; it < kCombine; it++) {
-    const unsigned long long m = __ballot(have);
-    if (m == 0ull) return;
-    const int leader = __ffsll((long long)m) - 1;
-    const int key = __shfl(cell, leader);
-    const bool mine = have && cell == key;
-    uint32_t sum = mine ? cnt : 0u;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
-    if (lane == leader) atomicAdd(&acc[key], sum);
-    if (mine) have = false;
-  }
-  if (have) atomicAdd(&acc[cell], cnt);
-}
 
 // bins [n][bins] (in the caller's dBins, as order-encoded uint64 until k_spx_finish), extrema [n][4], acc [n][cells] (may be null)
 __global__ void __launch_bounds__(256) k_spx_init(long long total_bins, int n, long long total_cells, unsigned long long* __restrict__ gbins,
@@ -120,20 +32,20 @@ __global__ void __launch_bounds__(256) k_spx_init(long long total_bins, int n, l
 // the frame's bins / extrema (and, kCostmap, its cell counts).
 // k_scan's work shape: one thread per column, kSpxRows rows, the thread's loads requested together.  What differs: the rows are visited
 // by the whole wave TOGETHER (the loop counter is wave-uniform, a row nobody needs is skipped by the wave), so that the cell counts can be
-// combined across the wave (spx_wave_add is convergent) and the row's terms of the reprojection are the same in every lane.
+// combined across the wave (nav_wave_add is convergent) and the row's terms of the reprojection are the same in every lane.
 // An obstacle is a near-vertical surface: consecutive rows of a column fall in the same bin and mostly in the same cell, so a thread keeps
 // (bin, running minimum) and (cell, count) in registers and goes to the LDS / the accumulation grid once per RUN of rows.
 constexpr int kSpxRows = 16;
 template <int FMT, bool kCostmap>
 __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __restrict__ disp_, int W, int H, unsigned long long* __restrict__ gbins,
                                                         unsigned long long* __restrict__ gmeta, uint32_t* __restrict__ acc) {
-  using T = typename Elem<FMT>::T;
+  using T = typename DispElem<FMT>::T;
   const T* __restrict__ disp = static_cast<const T*>(disp_);
   extern __shared__ unsigned long long lds[];      // [bins] + 4
   unsigned long long* lbins = lds;
-  unsigned long long* lmeta = lds + s.bins;
+  unsigned long long* lmeta = lds + s.g.bins;
   const int frame = blockIdx.z;
-  for (int k = threadIdx.x; k < s.bins; k += 256) lbins[k] = ~0ull;
+  for (int k = threadIdx.x; k < s.g.bins; k += 256) lbins[k] = ~0ull;
   if (threadIdx.x < 4) lmeta[threadIdx.x] = (threadIdx.x & 1) ? 0ull : ~0ull;
   __syncthreads();
   const int i = blockIdx.x * 256 + threadIdx.x, j0 = blockIdx.y * kSpxRows;
@@ -145,7 +57,7 @@ __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __
     for (int r = 0; r < kSpxRows; r++) raw[r] = disp[((size_t)frame * H + min(j0 + r, H - 1)) * W + i];
 #pragma unroll
     for (int r = 0; r < kSpxRows; r++)
-      if (spx_to_q<FMT>(raw[r], s.min_q, qv[r]) && j0 + r < H) cand |= 1u << r;
+      if (disp_to_q<FMT>(raw[r], s.min_q, qv[r]) && j0 + r < H) cand |= 1u << r;
   } else {
 #pragma unroll
     for (int r = 0; r < kSpxRows; r++) qv[r] = 0;
@@ -155,7 +67,7 @@ __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __
   unsigned long long cur_min = ~0ull;
   int cur_cell = -1;
   uint32_t cur_cnt = 0;
-  uint32_t* __restrict__ facc = kCostmap ? acc + (size_t)frame * s.cx * s.cy : nullptr;
+  uint32_t* __restrict__ facc = kCostmap ? acc + (size_t)frame * s.c.cx * s.c.cy : nullptr;
 #pragma unroll 1
   for (int r = 0; r < kSpxRows; r++) {
     const bool on = (cand >> r) & 1u;
@@ -168,15 +80,14 @@ __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __
 #pragma unroll
       for (int k = 1; k < kSpxRows; k++) q = (r == k) ? qv[k] : q;
       double X = 0, Y = 0, Z = 0;
-      const bool take = spx_reproject(s, i, j0 + r, q, X, Y, Z) && !spx_is_ground(s, X, Z);
+      const bool take = nav_reproject(s.g, i, j0 + r, __dmul_rn((double)q, 0.0625), X, Y, Z) && !nav_is_ground(s.g, X, Z);   // q / 16.0, exact
       if (take) {
         const double th = atan2(Y, X);
-        const double deg = __dmul_rn(th, 180.) / s.pi;
         const double rg = sqrt(__dadd_rn(__dmul_rn(Y, Y), __dmul_rn(X, X)));
-        const unsigned long long et = spx_enc(th), er = spx_enc(rg);
+        const unsigned long long et = nav_enc(th), er = nav_enc(rg);
         tmin = min(tmin, et); tmax = max(tmax, et); rmin = min(rmin, er); rmax = max(rmax, er);
-        const double kf = floor(__dmul_rn((double)s.bins, __dadd_rn(s.fov / 2., -deg)) / s.fov);  // :263, as k_scan
-        if (kf >= 0 && kf < (double)s.bins) {
+        const double kf = nav_bin(s.g, th);
+        if (kf >= 0 && kf < (double)s.g.bins) {
           const int k = (int)kf;
           if (k != cur_bin) {
             if (cur_bin >= 0) atomicMin(&lbins[cur_bin], cur_min);
@@ -186,10 +97,7 @@ __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __
       }
       if (kCostmap) {
         int cell = -1;
-        if (take && isfinite(X) && isfinite(Y) && isfinite(Z)) {                                  // jn_costmap.h "cell", as k_costmap_accumulate
-          const double fx = floor((X - s.org_x) / s.res), fy = floor((Y - s.org_y) / s.res);
-          if (fx >= 0. && fx < (double)s.cx && fy >= 0. && fy < (double)s.cy) cell = (int)fy * s.cx + (int)fx;
-        }
+        if (take) cell = nav_cell(s.c, X, Y, Z);
         if (cell == cur_cell) cur_cnt++;
         else {
           if (cur_cell >= 0) { flush = true; fcell = cur_cell; fcnt = cur_cnt; }
@@ -197,10 +105,10 @@ __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __
         }
       }
     }
-    if (kCostmap) { if (__any(flush)) spx_wave_add(flush, fcell, fcnt, facc); }
+    if (kCostmap) { if (__any(flush)) nav_wave_add(flush, fcell, fcnt, facc); }
   }
   if (cur_bin >= 0) atomicMin(&lbins[cur_bin], cur_min);
-  if (kCostmap) spx_wave_add(cur_cell >= 0, cur_cell, cur_cnt, facc);
+  if (kCostmap) nav_wave_add(cur_cell >= 0, cur_cell, cur_cnt, facc);
   // extrema: butterfly inside the wave, then one LDS atomic per wave — skipped by the waves in which no pixel was an obstacle
   if (__ballot(tmin != ~0ull) != 0ull) {
 #pragma unroll
@@ -212,8 +120,8 @@ __global__ void __launch_bounds__(256) k_spx_accumulate(SpxDev s, const void* __
   }
   __syncthreads();
   // one device-scope atomic per touched bin and workgroup
-  for (int k = threadIdx.x; k < s.bins; k += 256)
-    if (lbins[k] != ~0ull) atomicMin(&gbins[(size_t)frame * s.bins + k], lbins[k]);
+  for (int k = threadIdx.x; k < s.g.bins; k += 256)
+    if (lbins[k] != ~0ull) atomicMin(&gbins[(size_t)frame * s.g.bins + k], lbins[k]);
   if (threadIdx.x < 4) {
     const unsigned long long x = lmeta[threadIdx.x];
     if (threadIdx.x & 1) { if (x != 0ull) atomicMax(&gmeta[frame * 4 + threadIdx.x], x); }
@@ -227,24 +135,24 @@ __global__ void __launch_bounds__(256) k_spx_finish(long long total_bins, int n,
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t < total_bins) {
     const unsigned long long k = gbins[t];
-    reinterpret_cast<double*>(gbins)[t] = (k == ~0ull) ? JN_SCAN_EMPTY : spx_dec(k);
+    reinterpret_cast<double*>(gbins)[t] = (k == ~0ull) ? JN_SCAN_EMPTY : nav_dec(k);
   }
   if (t < (long long)n * 4) {
     const unsigned long long k = gmeta[t];
     const double init[4] = {400., -400., 1e9, -500.};
     const bool untouched = (t & 1) ? (k == 0ull) : (k == ~0ull);
-    meta[t] = untouched ? init[t & 3] : spx_dec(k);
+    meta[t] = untouched ? init[t & 3] : nav_dec(k);
   }
 }
 
 // Point cloud: k_pc_*'s shape (counts per column, exclusive scan, ordered write), over valid pixels.  col_count: [W + 1] int64.
 template <int FMT>
 __global__ void __launch_bounds__(256) k_spx_pc_count(const void* __restrict__ disp_, int min_q, int W, int H, long long* __restrict__ col_count) {
-  const typename Elem<FMT>::T* __restrict__ disp = static_cast<const typename Elem<FMT>::T*>(disp_);
+  const typename DispElem<FMT>::T* __restrict__ disp = static_cast<const typename DispElem<FMT>::T*>(disp_);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= W) return;
   int c = 0, q;
-  for (int j = 0; j < H; j++) c += spx_to_q<FMT>(disp[(size_t)j * W + i], min_q, q) ? 1 : 0;
+  for (int j = 0; j < H; j++) c += disp_to_q<FMT>(disp[(size_t)j * W + i], min_q, q) ? 1 : 0;
   col_count[i + 1] = c;
   if (i == 0) col_count[0] = 0;
 }
@@ -254,37 +162,28 @@ __global__ void k_spx_pc_scan(int W, long long* col_count) {   // tiny: one thre
 template <int FMT>
 __global__ void __launch_bounds__(256) k_spx_pc_scatter(SpxDev s, const void* __restrict__ disp_, int W, int H,
                                                         const long long* __restrict__ col_count, float* __restrict__ xyz) {
-  const typename Elem<FMT>::T* __restrict__ disp = static_cast<const typename Elem<FMT>::T*>(disp_);
+  const typename DispElem<FMT>::T* __restrict__ disp = static_cast<const typename DispElem<FMT>::T*>(disp_);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= W) return;
   long long o = col_count[i];
   for (int j = 0; j < H; j++) {
     int q;
-    if (!spx_to_q<FMT>(disp[(size_t)j * W + i], s.min_q, q)) continue;
+    if (!disp_to_q<FMT>(disp[(size_t)j * W + i], s.min_q, q)) continue;
     double X, Y, Z;
-    if (!spx_reproject(s, i, j, q, X, Y, Z)) { X = Y = Z = 0; }
+    if (!nav_reproject(s.g, i, j, __dmul_rn((double)q, 0.0625), X, Y, Z)) { X = Y = Z = 0; }
     xyz[3 * o] = (float)X; xyz[3 * o + 1] = (float)Y; xyz[3 * o + 2] = (float)Z; o++;
   }
 }
 
 SpxDev spx_to_dev(const jn_scan_params& sp, const jn_costmap_params* cp, const jn_subpix_params& fp) {
-  SpxDev s;
-  for (int i = 0; i < 16; i++) s.Q[i] = sp.Q[i];
-  for (int i = 0; i < 9; i++) s.XR[i] = sp.XR[i];
-  for (int i = 0; i < 3; i++) s.XT[i] = sp.XT[i];
-  s.ox = sp.crop_offset_x; s.oy = sp.crop_offset_y;
-  s.gp_h = sp.gp_height_thresh; s.gp_tan = tan(sp.gp_angle_thresh); s.gp_dist = sp.gp_dist_thresh;
-  s.fov = sp.fov_deg; s.pi = sp.pi_approx; s.bins = sp.bins; s.min_q = fp.min_q;
-  s.org_x = cp ? cp->origin_x : 0.; s.org_y = cp ? cp->origin_y : 0.; s.res = cp ? cp->resolution : 1.;
-  s.cx = cp ? cp->cells_x : 0; s.cy = cp ? cp->cells_y : 0;
-  return s;
+  return SpxDev{nav_geom(sp), cp ? nav_grid(*cp) : NavGrid{0., 0., 1., 0, 0}, fp.min_q};
 }
 
 template <bool kCostmap>
 void spx_launch_accumulate(hipStream_t st, const SpxDev& s, int format, int n, const void* disp, int W, int H, unsigned long long* gbins,
                            unsigned long long* gmeta, uint32_t* acc) {
   const dim3 g((W + 255) / 256, (H + kSpxRows - 1) / kSpxRows, n);
-  const size_t lds = (s.bins + 4) * sizeof(unsigned long long);
+  const size_t lds = (s.g.bins + 4) * sizeof(unsigned long long);
   if (format == JN_DISP_F32) hipLaunchKernelGGL((k_spx_accumulate<JN_DISP_F32, kCostmap>), g, dim3(256), lds, st, s, disp, W, H, gbins, gmeta, acc);
   else if (format == JN_DISP_I16) hipLaunchKernelGGL((k_spx_accumulate<JN_DISP_I16, kCostmap>), g, dim3(256), lds, st, s, disp, W, H, gbins, gmeta, acc);
   else hipLaunchKernelGGL((k_spx_accumulate<JN_DISP_I16_SUB, kCostmap>), g, dim3(256), lds, st, s, disp, W, H, gbins, gmeta, acc);
@@ -333,39 +232,16 @@ void launch_subpix_point_cloud(hipStream_t st, const jn_scan_params& sp, const j
 
 using namespace jnav;
 
-#define SPX_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
-
 namespace {
-
-// grow-only scratch per device and calling thread, as the scan's and the costmap's: no hipMalloc / hipFree (a device-wide sync) per call
-jn_status spx_scratch(int device, size_t need, void** out) {
-  struct Scratch { void* p = nullptr; size_t cap = 0; int dev = -1; };
-  static thread_local Scratch sc;
-  if (sc.dev != device || sc.cap < need) {
-    if (sc.p) { hipSetDevice(sc.dev); hipFree(sc.p); hipSetDevice(device); sc.p = nullptr; sc.cap = 0; }
-    SPX_TRY(hipMalloc(&sc.p, need));
-    sc.cap = need; sc.dev = device;
-  }
-  *out = sc.p;
-  return JN_OK;
-}
 
 jn_status spx_sync_call(int32_t device, const jn_scan_params* sp, const jn_costmap_params* cp, const jn_subpix_params* fp, int32_t n, const void* dDisp,
                         int32_t W, int32_t H, double* dBins, double* dMeta, uint16_t* dHits, int8_t* dGrid) {
-  SPX_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   void* scratch = nullptr;
-  const jn_status es = spx_scratch(device, subpix_scratch_bytes(cp, n), &scratch);
-  if (es != JN_OK) return es;
+  HIP_TRY(thread_scratch(device, subpix_scratch_bytes(cp, n), &scratch));
   launch_subpix(nullptr, *sp, cp, *fp, n, dDisp, W, H, dBins, dMeta, dHits, dGrid, scratch);
-  SPX_TRY(hipStreamSynchronize(nullptr));
-  SPX_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 
@@ -394,16 +270,15 @@ jn_status jn_subpix_costmap(int32_t device, const jn_scan_params* sp, const jn_c
 jn_status jn_subpix_point_cloud(int32_t device, const jn_scan_params* sp, const jn_subpix_params* fp, const void* dDisp, int32_t W, int32_t H,
                                 float* dXyz, int64_t* count) {
   if (!sp || !subpix_params_valid(fp) || !dDisp || !dXyz || !count || W < 1 || H < 1) return JN_ERR_INVALID;
-  SPX_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   void* scratch = nullptr;
-  const jn_status es = spx_scratch(device, sizeof(long long) * ((size_t)W + 1), &scratch);
-  if (es != JN_OK) return es;
+  HIP_TRY(thread_scratch(device, sizeof(long long) * ((size_t)W + 1), &scratch));
   long long* cols = static_cast<long long*>(scratch);
   launch_subpix_point_cloud(nullptr, *sp, *fp, dDisp, W, H, dXyz, cols);
   long long total = 0;
-  SPX_TRY(hipMemcpy(&total, cols + W, sizeof(long long), hipMemcpyDeviceToHost));
-  SPX_TRY(hipStreamSynchronize(nullptr));
-  SPX_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(&total, cols + W, sizeof(long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   *count = total;
   return JN_OK;
 }

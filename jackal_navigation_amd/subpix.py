@@ -78,13 +78,4 @@ def attach(handle, slot, cp=None, dBins=None, dMeta=None, dHits=None, dGrid=None
     """From now on every scan batch submitted on `slot` of an Elas or Sgm handle also writes the sub-pixel scan into dBins / dMeta and,
     with cp, the costmap into dHits / dGrid (valid after the slot's wait).  Everything None detaches.  No batch may be in flight on the
     slot."""
-    from .elas import Elas
-    from .sgm import Sgm
-    L = _bind()
-    if isinstance(handle, Elas):
-        fn, what = L.jn_elas_attach_subpix, "jn_elas_attach_subpix"
-    elif isinstance(handle, Sgm):
-        fn, what = L.jn_sgm_attach_subpix, "jn_sgm_attach_subpix"
-    else:
-        raise TypeError("attach() takes an Elas or an Sgm handle; block-matching users call subpix_costmap() after Bm.wait()")
-    _lib.check(fn(handle._h, slot, C.byref(cp) if cp is not None else None, dBins, dMeta, dHits, dGrid), what)
+    _lib.attach_tail(_bind(), "subpix", handle, slot, cp, dBins, dMeta, dHits, dGrid, alternative="subpix_costmap()")
