@@ -6,6 +6,7 @@
 #include "../../include/jn_stereo.h"
 #include "../../include/jn_costmap.h"
 #include "../../include/jn_subpix.h"
+#include "../../include/jn_postfilter.h"
 
 namespace jnav {
 
@@ -153,5 +154,13 @@ void launch_subpix(hipStream_t st, const jn_scan_params& sp, const jn_costmap_pa
 // col_count: [W+1] int64 scratch
 void launch_subpix_point_cloud(hipStream_t st, const jn_scan_params& sp, const jn_subpix_params& fp, const void* disp, int W, int H, float* xyz,
                                long long* col_count);
+
+// Disparity post-filter (include/jn_postfilter.h; postfilter.hip) -------------------------------------
+bool postfilter_params_valid(const jn_postfilter_params* fp);
+// labels and sizes (one u32 each per pixel, with a speckle stage) and, for a median with in == out, a copy of the maps
+size_t postfilter_scratch_bytes(const jn_postfilter_params& fp, int n, int W, int H, bool in_place);
+// The clear of stats (may be null) and every phase on `st`: in [n][H][W] int16 -> out (may be in).  Errors: the clear's, the copy's.
+hipError_t launch_postfilter(hipStream_t st, const jn_postfilter_params& fp, int n, const int16_t* in, int W, int H, int16_t* out, uint32_t* stats,
+                             void* scratch);
 
 }  // namespace jnav

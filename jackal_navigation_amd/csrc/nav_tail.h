@@ -44,13 +44,15 @@ inline hipError_t thread_scratch(int device, size_t bytes, void** out) {
 }
 
 // The tails attached to one slot of an ELAS or SGM handle (jn_*_attach_costmap, include/jn_costmap.h; jn_*_attach_subpix,
-// include/jn_subpix.h) and their device scratch.  A plain value: a copy refers to the same scratch, release() frees it.  The handle
+// include/jn_subpix.h; jn_sgm_attach_postfilter, include/jn_postfilter.h) and their device scratch.  A plain value: a copy refers to the same scratch, release() frees it.  The handle
 // calls attach_* only while the slot is idle, so nothing reads the scratch a call replaces.
 struct NavTails {
   struct Costmap { bool on = false; jn_costmap_params cp = {}; uint16_t* hits = nullptr; int8_t* grid = nullptr; };
   struct Subpix { bool on = false, has_cp = false; jn_costmap_params cp = {}; double* bins = nullptr; double* meta = nullptr; uint16_t* hits = nullptr; int8_t* grid = nullptr; };
   Costmap cm; void* cm_acc = nullptr; size_t cm_acc_bytes = 0;   // the accumulation grid [max_batch][cells] u32
   Subpix sx; void* sx_scratch = nullptr; size_t sx_bytes = 0;    // subpix_scratch_bytes(cp, max_batch)
+  struct Postfilter { bool on = false; jn_postfilter_params fp = {}; uint32_t* stats = nullptr; };
+  Postfilter pf; void* pf_scratch = nullptr; size_t pf_bytes = 0; // postfilter_scratch_bytes(fp, max_batch, W, H, in place)
 
   static jn_status grow(int device, size_t need, void** p, size_t* cap) {
     if (need <= *cap) return JN_OK;
@@ -84,6 +86,21 @@ struct NavTails {
     return JN_OK;
   }
 
+  // fp == nullptr detaches; `native`: the format of the handle's maps (a jn_disp_format)
+  jn_status attach_postfilter(int device, int max_batch, int W, int H, int native, const jn_postfilter_params* fp, uint32_t* dStats) {
+    if (!fp) { pf = Postfilter(); return JN_OK; }
+    if (!postfilter_params_valid(fp) || fp->format != native) return JN_ERR_INVALID;
+    const jn_status e = grow(device, postfilter_scratch_bytes(*fp, max_batch, W, H, true), &pf_scratch, &pf_bytes);
+    if (e != JN_OK) return e;
+    pf.on = true; pf.fp = *fp; pf.stats = dStats;
+    return JN_OK;
+  }
+
+  // Ahead of everything that consumes the matcher's map, on the batch's stream: the attached post-filter, in place.
+  hipError_t launch_postfilter_in_place(hipStream_t st, int n, int16_t* dDisp, int W, int H) const {
+    return pf.on ? launch_postfilter(st, pf.fp, n, dDisp, W, H, dDisp, pf.stats, pf_scratch) : hipSuccess;
+  }
+
   // Behind a scan batch, on its stream: the costmap of the mono8 map and the bins the scan has just written, then the sub-pixel tail of the
   // matcher's own map (`native`, in `format`: a jn_disp_format) with the default min_q.  The only error is the costmap's clear.
   hipError_t launch(hipStream_t st, const jn_scan_params& sp, int n, const uint8_t* dDispU8, const uint8_t* dLut, const double* dBins,
@@ -101,7 +118,7 @@ struct NavTails {
   }
 
   void release() {
-    (void)hipFree(cm_acc); (void)hipFree(sx_scratch);
+    (void)hipFree(cm_acc); (void)hipFree(sx_scratch); (void)hipFree(pf_scratch);
     *this = NavTails();
   }
 };

@@ -14,6 +14,7 @@
 #include "../../include/jn_sgm.h"
 #include "../../include/jn_costmap.h"
 #include "../../include/jn_subpix.h"
+#include "../../include/jn_postfilter.h"
 #include "sgm_sweep.h"
 #include "nav_tail.h"           // kernels.h's launch_scan, and NavTails: the node's tails on a slot's stream (jn_sgm_submit_scan)
 
@@ -177,8 +178,12 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
   // With a scan: ONE tail kernel applies the L/R check, writes the int16 map and the mono8 map (point_cloud.cpp:422 semantics) and scans
   // (JN_SGM_TAIL=3: the three kernels k_sw_lr, k_sgm_to_u8, k_scan one after the other, for A/B).
   static const bool fused_tail = !(getenv("JN_SGM_TAIL") && atoi(getenv("JN_SGM_TAIL")) == 3);
-  const bool fuse = sp && fused_tail;
+  // An attached post-filter (include/jn_postfilter.h) sits between the L/R check and everything that reads the map, so the one-kernel tail
+  // cannot be used: such a slot queues the three kernels, with the filter in place on dDisp behind the first.
+  const jnav::NavTails& tails = h->tails[slot];
+  const bool fuse = sp && fused_tail && !tails.pf.on;
   HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, sb, ev, false, !fuse));
+  HIP_TRY(tails.launch_postfilter_in_place(st, n, dDisp, h->W, h->H));
   if (fuse) {
     jnav::SgmWinners w;
     w.dl = sb.dl; w.minr = sb.minr; w.disp = dDisp; w.lr = h->sw.lr; w.subpixel = h->sw.subpixel;
@@ -190,7 +195,7 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
   }
   if (sp) {                                                     // the attached tails: the costmap of the mono8 map and the bins just written, the sub-pixel tail of the int16 map
     const int native = h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16;
-    HIP_TRY(h->tails[slot].launch(st, *sp, n, dDispU8, dLut, dBins, dDisp, native, h->W, h->H));
+    HIP_TRY(tails.launch(st, *sp, n, dDispU8, dLut, dBins, dDisp, native, h->W, h->H));
   }
   // the batch's end: behind the scan tail, not behind the sweeps (ev[3] stays the end of the winner-takes-all timing)
   if (!h->ev_end[slot]) HIP_TRY(hipEventCreateWithFlags(&h->ev_end[slot], hipEventDisableTiming));
@@ -210,6 +215,12 @@ jn_status jn_sgm_attach_subpix(jn_sgm* h, int32_t slot, const jn_costmap_params*
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
   if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
   return h->tails[slot].attach_subpix(h->device, h->max_batch, cp, dBins, dMeta, dHits, dGrid);
+}
+
+jn_status jn_sgm_attach_postfilter(jn_sgm* h, int32_t slot, const jn_postfilter_params* fp, uint32_t* dStats) {
+  if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
+  if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
+  return h->tails[slot].attach_postfilter(h->device, h->max_batch, h->W, h->H, h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16, fp, dStats);
 }
 
 jn_status jn_sgm_wait(jn_sgm* h, int32_t slot) {

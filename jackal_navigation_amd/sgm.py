@@ -71,6 +71,12 @@ class Sgm:
         from . import subpix
         subpix.attach(self, slot, cp, dBins, dMeta, dHits, dGrid)
 
+    def attach_postfilter(self, slot, fp=None, dStats=None):
+        """The disparity post-filter (include/jn_postfilter.h) in place on every batch of `slot`, ahead of everything that reads the map;
+        fp = None detaches."""
+        from . import postfilter
+        postfilter.attach(self, slot, fp, dStats)
+
     def wait(self, slot):
         _lib.check(self._L.jn_sgm_wait(self._h, slot), "jn_sgm_wait")
 
