@@ -14,6 +14,8 @@ from . import costmap  # noqa: F401
 from .costmap import CostmapParams, COSTMAP_EXPORTS  # noqa: F401
 from . import subpix  # noqa: F401
 from .subpix import SubpixParams, SUBPIX_EXPORTS, subpix_scan, subpix_costmap, subpix_point_cloud  # noqa: F401
+from . import localmap  # noqa: F401
+from .localmap import LocalMap, LocalMapParams, Pose2D, LOCALMAP_EXPORTS, localmap_params  # noqa: F401
 from . import postfilter  # noqa: F401
 from .postfilter import PostfilterParams, POSTFILTER_EXPORTS, postfilter_params, disparity_postfilter  # noqa: F401
 from . import ground, calib  # noqa: F401
