@@ -10,10 +10,11 @@
 //                 [-> u8 map + obstacle scan when submitted through jn_elas_submit_scan]
 // Several slots in flight overlap one batch's host stage with another batch's GPU stages.
 // Batch handles of processes with few cores of their own have NO host stage: the hull recursion runs on the GPU too (delaunay_gpu.hip),
-// FrameInfo and the payload are written on the device and stage B is queued right behind it (run_batch_route).
+// FrameInfo and the payload are written on the device and stage B is queued right behind it (finish_gpu_route).
 #include "../../include/jn_stereo.h"
 #include "hooks.h"
 #include "kernels.h"
+#include "dev_owner.h"
 #include "nav_tail.h"
 #include "host_stage.h"
 #include "pool.h"
@@ -55,13 +56,16 @@ struct Job {
 enum { EV_BEGIN, EV_DESC, EV_SUPPORT, EV_D2H, EV_H2D0, EV_H2D, EV_RASTER, EV_DENSE, EV_LR, EV_SPECKLE, EV_GAP, EV_AM, EV_END, EV_COUNT };
 
 struct Slot {
+  // Everything jn_elas_create makes for the slot is recorded here and released by jn_elas_destroy in one call.  What is made later keeps
+  // its own release: st_img / st_D (run_batch_host frees a half-made pair itself) and the tails' scratch (NavTails::release).
+  DevOwner own;
   hipStream_t stream = nullptr;
-  hipEvent_t ev_scan = nullptr, ev_merged = nullptr;          // around the cross-rig merge (created with the slot)
+  hipEvent_t ev_merged = nullptr;                              // behind the cross-rig merge (created with the slot)
   hipEvent_t ev_head = nullptr;                                // behind the heavy head of stage A (descriptors + support matches): start-up pacing
   float merge_ms = 0.f;
   double* d_flat = nullptr;                                   // the merge's packed buffer of this slot [max_batch][1024 + 4] (written by k_scan_finish)
-  hipStream_t stream_a = nullptr;                             // highest-priority stream for stage A (see run_batch); only with JN_STAGE_A_PRIORITY=1
-  uint32_t* gate = nullptr; uint32_t gate_seq = 0;            // latency mode: the word stage B's queued launches wait on (hipMallocSignalMemory), see run_batch
+  hipStream_t stream_a = nullptr;                             // highest-priority stream for stage A (see Batch); only with JN_STAGE_A_PRIORITY=1
+  uint32_t* gate = nullptr; uint32_t gate_seq = 0;            // latency mode: the word stage B's queued launches wait on (hipMallocSignalMemory), see GateGuard
   hipEvent_t ev[EV_COUNT] = {};
   // device
   uint4* desc = nullptr; uint8_t* planes = nullptr; int16_t* d_can = nullptr;   // descriptors: materialised (the old flow) OR the two Sobel planes (h->plane_flow)
@@ -115,7 +119,7 @@ struct jn_elas {
   // take the lattice.
   int filter_min_batch = 4;
   int wait_spin_us = 60;            // JN_WAIT_SPIN_US; 1000 for max_batch == 1 (see wait_event)
-  bool stage_events = true;         // JN_STAGE_EVENTS: default on, off for max_batch == 1 (see run_batch)
+  bool stage_events = true;         // JN_STAGE_EVENTS: default on, off for max_batch == 1 (see Batch)
   bool gpu_arrange = true;          // JN_GPU_ARRANGE=0: the host computes the alternating-cut arrangement itself (A/B, tests)
   int arr_cap = 0, arr_stride = 0;  // vertices per frame side k_arrange orders in LDS / at all (more: in global scratch / on the host)
   int dt_gcap = 0;                  // GPU triangulation: vertices per side beyond one workgroup's LDS that the global scratch lets through (0: none)
@@ -135,7 +139,7 @@ struct jn_elas {
   bool arrange_sorts = false;       // hooks build, JN_ARRANGE_SORTS=1: k_arrange's sort forms where its rank form would run (A/B, tests)
   bool gpu_delaunay = false;        // batch handles: the triangulations' hull recursion on the GPU too (delaunay_gpu.hip; JN_GPU_DELAUNAY=0/1), no host stage
   bool plane_flow = true;           // descriptors assembled from the Sobel planes inside the matching kernels (JN_DESC_FLOW=desc: materialised, the old flow)
-  std::atomic<bool> gate_stage_b{false};   // latency mode: stage B is queued behind a gate while the GPU runs stage A (JN_GATE_STAGE_B=0/1), see run_batch
+  std::atomic<bool> gate_stage_b{false};   // latency mode: stage B is queued behind a gate while the GPU runs stage A (JN_GATE_STAGE_B=0/1), see GateGuard
   uint64_t submit_seq = 0, merge_seq = 0;                     // next number handed to a scan batch / next batch allowed to queue its merge
   std::vector<uint64_t> merge_log;                            // submission numbers in the order their merges were queued (the last 4096; jn_elas_merge_order)
   int comm_timeout_ms = 30000;                                // JN_COMM_TIMEOUT_MS: a merge not complete by then is aborted (0: wait for ever)
@@ -164,28 +168,16 @@ namespace {
 // tightly for the first 60 us, then between short sleeps (a batch's stage lasts milliseconds; the other slots keep the GPU
 // busy meanwhile).  A latency-mode handle (max_batch 1) polls tightly for 1 ms: its stages are short and a sleep's wake-up
 // would show in every call.  JN_WAIT_SPIN_US overrides (-1: plain hipEventSynchronize).
-hipError_t wait_event(hipEvent_t ev, int spin_us) {
-  if (spin_us < 0) return hipEventSynchronize(ev);
+// With a deadline (timeout_ms > 0): hipErrorNotReady when it passed without the event completing.
+hipError_t wait_event(hipEvent_t ev, int spin_us, int timeout_ms = 0) {
+  if (spin_us < 0 && timeout_ms <= 0) return hipEventSynchronize(ev);
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     const hipError_t e = hipEventQuery(ev);
     if (e != hipErrorNotReady) return e;
     const auto waited = std::chrono::steady_clock::now() - t0;
+    if (timeout_ms > 0 && waited > std::chrono::milliseconds(timeout_ms)) return hipErrorNotReady;
     if (waited < std::chrono::microseconds(spin_us)) { __builtin_ia32_pause(); continue; }
-    std::this_thread::sleep_for(std::chrono::microseconds(waited < std::chrono::microseconds(500) ? 20 : 50));
-  }
-}
-
-// The same with a deadline: hipErrorNotReady when `timeout_ms` (> 0) passed without the event completing.
-hipError_t wait_event_bounded(hipEvent_t ev, int spin_us, int timeout_ms) {
-  if (timeout_ms <= 0) return wait_event(ev, spin_us);
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t e = hipEventQuery(ev);
-    if (e != hipErrorNotReady) return e;
-    const auto waited = std::chrono::steady_clock::now() - t0;
-    if (waited > std::chrono::milliseconds(timeout_ms)) return hipErrorNotReady;
-    if (waited < std::chrono::microseconds(std::max(spin_us, 0))) { __builtin_ia32_pause(); continue; }
     std::this_thread::sleep_for(std::chrono::microseconds(waited < std::chrono::microseconds(500) ? 20 : 50));
   }
 }
@@ -232,32 +224,114 @@ struct MergeTurn {
   }
 };
 
-jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bool force_host);
-jn_status run_batch(jn_elas* h, Slot& s, const Job& j) {
-  MergeTurn turn(h, j);
-  if (j.merge && h->test_fail_seq >= 0 && (long long)j.seq == h->test_fail_seq) return JN_ERR_INTERNAL;
-  return run_batch_route(h, s, j, turn, false);
-}
-// force_host: the triangulations on the host (the route of latency-mode handles, of parameter sets with corner points, and the second pass
-// of a batch whose frames the GPU's triangulation handed back)
-jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bool force_host) {
-  const DevParams& dp = h->dp;
-  const int n = j.n;
-  hipStream_t st = s.stream;
-  HIP_TRY(hipSetDevice(h->device));
-  auto t_begin = std::chrono::steady_clock::now();
-  // Stage boundaries for jn_elas_last_times.  A timing event between two kernels costs ~6 us of idle GPU: nothing when
-  // other slots fill the gap, 7 % of a lone 640x480 pair — a latency-mode handle (max_batch 1) leaves them out.
-  const bool stage_events = h->stage_events;
-  auto mark = [&](int e) { return stage_events ? hipEventRecord(s.ev[e], st) : hipSuccess; };
+// Latency mode (a handle of max_batch 1): a lone pair's stage B is two dozen launches of a few microseconds each, and queued after the
+// host stage they reach the GPU slower than it finishes them (~30 us of idle gaps at 640x480).  They are queued while the GPU runs
+// stage A instead, behind a wait on a word of signal memory that the host sets when its stage is done (hipStreamWaitValue32).  What
+// the host stage decides is then not known at launch time: the three launches sized by support / triangle counts take their capacity
+// (the kernels return on indices beyond the frame's counts), the payload and FrameInfo are read where the host will have written them,
+// and the two clears that depend on nothing run ahead of the gate.  Whatever happens afterwards, the gate is opened (GateGuard): a
+// stream left waiting would hang the handle.
+struct GateGuard {
+  volatile uint32_t* word = nullptr; uint32_t value = 0;
+  FrameInfo* info = nullptr; int n = 0; hipStream_t st = nullptr;
+  bool shut() const { return word != nullptr; }
+  void open() { if (word) { std::atomic_thread_fence(std::memory_order_seq_cst); *word = value; word = nullptr; } }
+  // An early return with the gate still shut: stage B is on the stream and WILL run once the gate opens, on whatever FrameInfo holds —
+  // the previous batch's, if the host stage never ran.  Every frame is therefore marked as failed first (the matching and the
+  // post-processing return on !ok; the scan tail still scans whatever D1 holds into the caller's buffers), and the stream is drained
+  // before the error goes back: the caller may free its buffers as soon as it has it.
+  ~GateGuard() {
+    if (!word) return;
+    for (int i = 0; i < n; i++) info[i].ok = 0;
+    open();
+    hipStreamSynchronize(st);
+  }
+};
+
+// What stage A decided while it was queued.
+struct StageA {
+  bool filtered = false;                                 // the device filters ran: the GPU lists the support points itself
+  bool arranged = false;                                 // k_arrange was launched for the triangulations to start from
+  bool gpu_dt = false;                                   // k_delaunay was launched: no host stage
+  bool grid_early = false;                               // the candidate grid is queued already
+};
+
+// Stage B as a function of what the host stage yields.
+struct StageBInput {
+  int max_sup, max_tri;                                  // the largest support / triangle counts (launch sizes), or their capacities where the counts are not known yet
+  bool any_ok;                                           // some frame has a triangulation
+  const uint8_t* payload; size_t payload_bytes;          // where the payload is read from: s.payload (and the bytes to copy there first) or pinned memory
+  bool cleared;                                          // the two clears were queued ahead
+  bool device_info;                                      // FrameInfo was written on the device: nothing to copy
+};
+
+// What the route of one pass leaves for run_batch.
+struct RouteResult {
+  std::chrono::steady_clock::time_point t_begin;
+  float host_ms = 0.f;                                   // the host stage on the worker's clock
+  bool any_ok = false;
+  bool handed_back = false;                              // GPU route: k_delaunay left a side to the host, the batch goes through the host route
+};
+
+// What one pass of a batch over a route works on.  Everything here is fixed before anything is queued; what only becomes known while
+// queueing is returned by the stage that decides it (StageA; the host stage's part of StageBInput).
+struct Batch {
+  jn_elas* h; Slot& s; const Job& j; const DevParams& dp;
+  int n;
   // Stage A (descriptors -> support matches -> filters -> list -> arrangement) ends in the host stage, which the whole batch
   // waits for; its small kernels (one workgroup per frame or side) would otherwise queue behind the dense kernels of the
   // other slots.  It runs on a stream of the highest priority; stage B stays on the slot's ordinary stream.  The two never
   // overlap within a slot (the worker waits for stage A, and for the batch's end before the next stage A), so no events tie
   // them together.  Host-pointer jobs stage their images on the ordinary stream and keep everything there.
-  hipStream_t sa = (s.stream_a && !j.staged) ? s.stream_a : st;
-  const DescSrc dsrc = h->plane_flow ? DescSrc{s.planes, plane_pitch(dp.W), true} : DescSrc{s.desc, 0, false};
-  auto mark_a = [&](int e) { return stage_events ? hipEventRecord(s.ev[e], sa) : hipSuccess; };
+  hipStream_t st, sa;
+  DescSrc dsrc;
+  // Stage boundaries for jn_elas_last_times.  A timing event between two kernels costs ~6 us of idle GPU: nothing when
+  // other slots fill the gap, 7 % of a lone 640x480 pair — a latency-mode handle (max_batch 1) leaves them out.
+  bool stage_events;
+  // the plan: the route decisions that do not depend on what the kernels find
+  int list_cap;                                          // support points a frame can hold: the lattice
+  // Where the list and the arrangement live: in device memory when this batch is going to triangulate on the GPU (everything that decides
+  // it is known here except whether the filter kernel lists the points itself: if it does not, the list goes to pinned memory and the host
+  // route is taken), in pinned host memory for the host stage.
+  bool want_gpu_dt;
+  int16_t* list_buf; int32_t* cnt_buf; uint16_t* arr_buf; int32_t* arr_ok_buf;
+  bool fused;                                            // gap interpolation and adaptive mean as one pass
+  bool grid_early_ok;                                    // the candidate grid may be queued behind stage A (see queue_stage_a)
+
+  hipError_t mark(int e) const { return stage_events ? hipEventRecord(s.ev[e], st) : hipSuccess; }
+  hipError_t mark_a(int e) const { return stage_events ? hipEventRecord(s.ev[e], sa) : hipSuccess; }
+  // one pass of the post-processing over the left map and, unless the parameters ask for the left one only, the right map
+  template <typename Pass>
+  void each_map(Pass&& pass) const { pass(j.dD1); if (!h->p.postprocess_only_left) pass(j.dD2); }
+
+  jn_status queue_stage_a(StageA* out) const;
+  jn_status queue_post_processing() const;
+  jn_status queue_stage_b(const StageA& a, const StageBInput& in) const;
+  jn_status queue_gated_stage_b(const StageA& a, GateGuard& gate, bool* cleared) const;
+  StageBInput host_stage(const StageA& a, float* ms) const;
+  jn_status finish_gpu_route(const StageA& a, RouteResult* out) const;
+  jn_status finish_host_route(const StageA& a, RouteResult* out) const;
+};
+
+// force_host: the triangulations on the host (the route of latency-mode handles, of parameter sets with corner points, and the second pass
+// of a batch whose frames the GPU's triangulation handed back)
+Batch plan_batch(jn_elas* h, Slot& s, const Job& j, bool force_host) {
+  const DevParams& dp = h->dp;
+  hipStream_t st = s.stream, sa = (s.stream_a && !j.staged) ? s.stream_a : st;
+  const bool want_gpu_dt = h->gpu_delaunay && !force_host && sa == st && s.d_list &&
+                           s.arr_hint <= (s.dt_scratch ? h->dt_gcap : delaunay_gpu_capacity(152 * 1024)) && h->gpu_arrange && s.arr_hint <= h->arr_stride;
+  static const bool grid_early_env = !(getenv("JN_GRID_EARLY") && atoi(getenv("JN_GRID_EARLY")) == 0);
+  return Batch{h, s, j, dp, j.n, st, sa,
+               h->plane_flow ? DescSrc{s.planes, plane_pitch(dp.W), true} : DescSrc{s.desc, 0, false},
+               h->stage_events, dp.cw * dp.ch, want_gpu_dt,
+               want_gpu_dt ? s.d_list : s.h_list, want_gpu_dt ? s.d_cnt : s.h_cnt, want_gpu_dt ? s.d_arr : s.h_arr, want_gpu_dt ? s.d_arr_ok : s.h_arr_ok,
+               gap_mean_fusable(dp, j.n) && ((dp.W * dp.H) & 3) == 0,
+               grid_early_env && !dp.add_corners && sa == st};
+}
+
+// Pacing, Sobel planes or descriptors, support matches, device filters, list, arrangement, triangulation or the candidates' copy to the
+// host, up to EV_D2H; behind it the candidate grid where it needs nothing of the host stage.
+jn_status Batch::queue_stage_a(StageA* out) const {
   {
     std::unique_lock<std::mutex> pl(h->pace_m, std::defer_lock);
     if (h->pace) {
@@ -271,15 +345,7 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
     launch_support(sa, dp, n, dsrc, s.d_can);
     if (h->pace) { HIP_TRY(hipEventRecord(s.ev_head, sa)); h->pace_prev = s.ev_head; }
   }
-  const int list_cap = dp.cw * dp.ch;
   bool listed = false;                                   // k_filter_resolve wrote the support list too
-  // Where the list and the arrangement live: in device memory when this batch is going to triangulate on the GPU (everything that decides
-  // it is known here except whether the filter kernel lists the points itself: if it does not, the list goes to pinned memory and the host
-  // route is taken), in pinned host memory for the host stage.
-  const bool want_gpu_dt = h->gpu_delaunay && !force_host && sa == st && s.d_list &&
-                           s.arr_hint <= (s.dt_scratch ? h->dt_gcap : delaunay_gpu_capacity(152 * 1024)) && h->gpu_arrange && s.arr_hint <= h->arr_stride;
-  int16_t* const list_buf = want_gpu_dt ? s.d_list : s.h_list; int32_t* const cnt_buf = want_gpu_dt ? s.d_cnt : s.h_cnt;
-  uint16_t* const arr_buf = want_gpu_dt ? s.d_arr : s.h_arr; int32_t* const arr_ok_buf = want_gpu_dt ? s.d_arr_ok : s.h_arr_ok;
   const bool filtered = (n >= h->filter_min_batch || (h->filter_min_batch < (1 << 30) && h->filters_fast)) &&
       launch_support_filters(sa, dp, n, h->p.incon_window_size, h->p.incon_threshold, h->p.incon_min_support, s.d_can, s.tmp, list_buf, cnt_buf, list_cap, &listed);
   HIP_TRY(mark_a(EV_SUPPORT));
@@ -299,12 +365,10 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
       const int want = s.arr_hint ? s.arr_hint + s.arr_hint / 4 + 64 : h->arr_cap;
       // more points than the LDS can order (1920x1080: 11 k): every side works in its slice of the global scratch, the launch asks for the minimum of LDS
       const int cap = s.arr_hint > h->arr_cap ? 1024 : std::min(h->arr_cap, std::max(1024, (want + 1023) / 1024 * 1024));
-      {
-        // (the global-scratch form only when the slot's recent batches held a side beyond the LDS form: at 1280x720 it would be an empty launch per batch)
-        const bool big = s.arr_scratch && (s.arr_hint == 0 || s.arr_hint > h->arr_cap);   // (0: the slot's first batch — nothing known yet)
-        launch_arrange(sa, n, list_buf, cnt_buf, list_cap, dp.step, cap, h->arr_stride, arr_buf, arr_ok_buf, big ? s.arr_scratch : nullptr, big ? h->arr_stride : 0,
-                       h->arrange_sorts ? ArrBounds{0, 0, 0, 0} : ArrBounds{dp.ch, dp.cw, -dp.disp_max, (dp.cw - 1) * dp.step + dp.disp_max + 1});
-      }
+      // (the global-scratch form only when the slot's recent batches held a side beyond the LDS form: at 1280x720 it would be an empty launch per batch)
+      const bool big = s.arr_scratch && (s.arr_hint == 0 || s.arr_hint > h->arr_cap);   // (0: the slot's first batch — nothing known yet)
+      launch_arrange(sa, n, list_buf, cnt_buf, list_cap, dp.step, cap, h->arr_stride, arr_buf, arr_ok_buf, big ? s.arr_scratch : nullptr, big ? h->arr_stride : 0,
+                     h->arrange_sorts ? ArrBounds{0, 0, 0, 0} : ArrBounds{dp.ch, dp.cw, -dp.disp_max, (dp.cw - 1) * dp.step + dp.disp_max + 1});
       if (gpu_dt)                                        // LDS for what the slot's last batches held + 6 % (a tight request: 32 bytes a vertex leave a k_dense_row workgroup room on the same CU); a side beyond it goes to the host
         HIP_TRY(launch_delaunay(sa, n, list_buf, cnt_buf, list_cap, dp.step, arr_buf, arr_ok_buf, h->arr_stride, s.arr_hint ? std::max(1024, s.arr_hint + s.arr_hint / 16 + 32) : (1 << 30), s.payload,
                                 (long long)h->payload_cap, s.info, s.need_host, nullptr, s.dt_scratch, h->dt_gcap, s.arr_hint, dp.W >= 2048 || dp.H >= 2048));
@@ -314,170 +378,150 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
     HIP_TRY(hipMemcpyAsync(s.h_can, s.d_can, can_bytes * n, hipMemcpyDeviceToHost, sa));
   }
   HIP_TRY(hipEventRecord(s.ev[EV_D2H], sa));
-
-  // ---- stage B, as a function of what the host stage yields: the largest support / triangle counts (launch sizes), whether any frame
-  // has a triangulation, where the payload is read from, and whether the two clears were queued ahead ----
-  const bool fused = gap_mean_fusable(dp, n) && ((dp.W * dp.H) & 3) == 0;
   // The candidate grid (elas.cpp:582-680) needs the support points, not the triangulation: without corner points they are the list the
   // GPU has just written, so the grid is queued HERE, behind stage A, and is built while the host triangulates (JN_GRID_EARLY=0: in stage B).
-  static const bool grid_early_env = !(getenv("JN_GRID_EARLY") && atoi(getenv("JN_GRID_EARLY")) == 0);
-  const bool grid_early = grid_early_env && filtered && !dp.add_corners && sa == st;
+  const bool grid_early = grid_early_ok && filtered;
   if (grid_early) launch_grid_from_list(st, dp, n, list_buf, cnt_buf, list_cap, s.mark, s.gridbits);
-  auto queue_stage_b = [&](int max_sup, int max_tri, bool any_ok, const uint8_t* payload, size_t payload_bytes, bool cleared, bool device_info = false) -> jn_status {
-    HIP_TRY(mark(EV_H2D0));
-    if (!device_info) HIP_TRY(hipMemcpyAsync(s.info, s.h_info, sizeof(FrameInfo) * n, hipMemcpyHostToDevice, st));
-    if (payload_bytes && payload == s.payload) HIP_TRY(hipMemcpyAsync(s.payload, s.h_payload, payload_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(mark(EV_H2D));
-    if (any_ok) {
-      if (!grid_early) launch_grid(st, dp, n, s.info, payload, 0, max_sup, s.mark, s.gridbits, !cleared);      // offsets in FrameInfo are batch-absolute
-      launch_bin(st, dp, n, s.info, s.recs, h->tri_cap, max_tri, s.bin_count, s.bin_list, !cleared, payload, 0);   // (forms the triangles' records on the way: k_tri_setup's work)
-      HIP_TRY(mark(EV_RASTER));
-      launch_dense(st, dp, n, s.info, s.recs, h->tri_cap, s.bin_count, s.bin_list, s.gridbits, dsrc, s.raw, false, (stage_events && h->plane_flow) ? s.ev_owner : nullptr);
-      HIP_TRY(mark(EV_DENSE));
-      // Post-processing.  When gap interpolation and adaptive mean can run as one pass (gap_mean_fusable), the left image
-      // travels raw -> tmp (L/R check) -> tmp (speckle, run lists in the still idle output image) -> D1 (fused pass), so that
-      // every stage reads and writes the image once; otherwise the stages run in place on D1 with tmp as scratch.
-      if (h->sub) {
-        // subsampling: the matcher ran on every pixel (findMatch is per pixel, so the reference's half-size map is the full one at even
-        // (u, v)); the L/R check picks those out, everything behind it works on (W/2) x (H/2) maps with dph
-        const DevParams& dph = h->dph;
-        launch_lr_sub(st, dp, n, s.info, s.raw, j.dD1, j.dD2);
-        HIP_TRY(mark(EV_LR));
-        launch_speckle(st, dph, n, s.info, j.dD1, s.label, s.size, s.tmp);
-        if (!h->p.postprocess_only_left) launch_speckle(st, dph, n, s.info, j.dD2, s.label, s.size, s.tmp);
-        HIP_TRY(mark(EV_SPECKLE));
-        launch_gap(st, dph, n, s.info, j.dD1, s.tmp);
-        if (!h->p.postprocess_only_left) launch_gap(st, dph, n, s.info, j.dD2, s.tmp);
-        HIP_TRY(mark(EV_GAP));
-        if (h->p.filter_adaptive_mean) {
-          launch_adaptive_mean_sub(st, dph, n, s.info, j.dD1, s.tmp);
-          if (!h->p.postprocess_only_left) launch_adaptive_mean_sub(st, dph, n, s.info, j.dD2, s.tmp);
-        }
-        if (h->p.filter_median) {
-          launch_median(st, dph, n, s.info, j.dD1, s.tmp);
-          if (!h->p.postprocess_only_left) launch_median(st, dph, n, s.info, j.dD2, s.tmp);
-        }
-        HIP_TRY(mark(EV_AM));
-      } else {
-      if (fused) {
-        launch_lr_speckle(st, dp, n, s.info, s.raw, s.tmp, j.dD2, s.label, s.size, j.dD1);   // (the L/R check and the speckle pass' row labelling are one kernel here)
-        HIP_TRY(mark(EV_LR));
-        HIP_TRY(mark(EV_SPECKLE));
-        launch_gap_mean_fused(st, dp, n, s.info, s.tmp, j.dD1, h->p.filter_adaptive_mean != 0);
-        if (!h->p.postprocess_only_left) {                     // right image: in place, fused pass into tmp, copied back
-          launch_speckle(st, dp, n, s.info, j.dD2, s.label, s.size, s.tmp);
-          launch_gap_mean_fused(st, dp, n, s.info, j.dD2, s.tmp, h->p.filter_adaptive_mean != 0);
-          launch_copy_ok(st, dp, n, s.info, s.tmp, j.dD2);
-        }
-        HIP_TRY(mark(EV_GAP));
-      } else {
-        launch_lr_speckle(st, dp, n, s.info, s.raw, j.dD1, j.dD2, s.label, s.size, s.tmp);   // L/R check of both maps + the left map's speckle pass (its row labelling in the L/R kernel)
-        HIP_TRY(mark(EV_LR));
-        if (!h->p.postprocess_only_left) launch_speckle(st, dp, n, s.info, j.dD2, s.label, s.size, s.tmp);
-        HIP_TRY(mark(EV_SPECKLE));
-        launch_gap(st, dp, n, s.info, j.dD1, s.tmp);
-        if (!h->p.postprocess_only_left) launch_gap(st, dp, n, s.info, j.dD2, s.tmp);
-        HIP_TRY(mark(EV_GAP));
-        if (h->p.filter_adaptive_mean) {
-          launch_adaptive_mean(st, dp, n, s.info, j.dD1, s.tmp);
-          if (!h->p.postprocess_only_left) launch_adaptive_mean(st, dp, n, s.info, j.dD2, s.tmp);
-        }
-      }
-      if (h->p.filter_median) {                                                            // elas.cpp:133-139
-        launch_median(st, dp, n, s.info, j.dD1, s.tmp);
-        if (!h->p.postprocess_only_left) launch_median(st, dp, n, s.info, j.dD2, s.tmp);
-      }
-      HIP_TRY(mark(EV_AM));
-      }
-    } else {
-      for (int e = EV_RASTER; e <= EV_AM; e++) HIP_TRY(mark(e));
-    }
-    if (j.scan)                                            // the node's tail: depth map + obstacle scan of whatever D1 now holds
-      launch_scan(st, j.sp, n, j.dD1, j.dDispU8, j.dLut, dp.W, dp.H, j.dBins, j.dMeta, s.scan_scratch, j.merge ? s.d_flat : nullptr);
-    if (j.scan) {                                          // the attached tails: the costmap of the map and the bins the scan has just written, the sub-pixel tail of the float map
-      const int native = JN_DISP_F32;
-      HIP_TRY(j.tails.launch(st, j.sp, n, j.dDispU8, j.dLut, j.dBins, j.dD1, native, dp.W, dp.H));
-    }
-    HIP_TRY(hipEventRecord(s.ev[EV_END], st));
-    return JN_OK;
-  };
-  auto t_host0 = std::chrono::steady_clock::now(), t_host1 = t_host0;
-  int any_ok = 0;
-  if (gpu_dt) {
-    any_ok = 1;
-    const jn_status qs = queue_stage_b(list_cap, h->tri_cap, true, s.payload, 0, false, true);
-    if (qs != JN_OK) return qs;
-    // what the host needs of the batch: which frames matched out (status), how many support points they held (the next launches' LDS),
-    // whether a side was handed back — copied behind everything else, read after the one wait
-    HIP_TRY(hipMemcpyAsync(s.h_info, s.info, sizeof(FrameInfo) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s.h_need, s.need_host, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(s.ev[EV_END], st));
-    HIP_TRY(wait_event(s.ev[EV_END], h->wait_spin_us));
-    HIP_TRY(hipGetLastError());
-    int batch_most = 0, handed_back = 0;
-    for (int i = 0; i < n; i++) { batch_most = std::max(batch_most, (int)s.h_info[i].reserved); handed_back |= s.h_need[i]; }   // (k_delaunay leaves the frame's support count, clipped or not, in `reserved`)
-    s.arr_hist[s.arr_pos] = batch_most; s.arr_pos = (s.arr_pos + 1) % Slot::kArrHist;
-    s.arr_hint = *std::max_element(s.arr_hist, s.arr_hist + Slot::kArrHist);
-    if (handed_back) {                                   // coinciding vertices or more of them than the launch's LDS held: the whole batch again, host stage and all
-      s.gpu_dt_fallbacks++;
-      return run_batch_route(h, s, j, turn, true);
-    }
-    for (int i = 0; i < n; i++) if (j.status) j.status[i] = s.h_info[i].ok ? JN_OK : JN_ERR_FEW_SUPPORT;
-  } else {
-  // Latency mode (a handle of max_batch 1): a lone pair's stage B is two dozen launches of a few microseconds each, and queued after the
-  // host stage they reach the GPU slower than it finishes them (~30 us of idle gaps at 640x480).  They are queued NOW instead, while the
-  // GPU runs stage A, behind a wait on a word of signal memory that the host sets when its stage is done (hipStreamWaitValue32).  What
-  // the host stage decides is then not known at launch time: the three launches sized by support / triangle counts take their capacity
-  // (the kernels return on indices beyond the frame's counts), the payload and FrameInfo are read where the host will have written them,
-  // and the two clears that depend on nothing run ahead of the gate.  Whatever happens afterwards, the gate is opened (GateGuard): a
-  // stream left waiting would hang the handle.
-  struct GateGuard {
-    volatile uint32_t* word = nullptr; uint32_t value = 0;
-    FrameInfo* info = nullptr; int n = 0; hipStream_t st = nullptr;
-    void open() { if (word) { std::atomic_thread_fence(std::memory_order_seq_cst); *word = value; word = nullptr; } }
-    // An early return with the gate still shut: stage B is on the stream and WILL run once the gate opens, on whatever FrameInfo holds —
-    // the previous batch's, if the host stage never ran.  Every frame is therefore marked as failed first (the matching and the
-    // post-processing return on !ok; the scan tail still scans whatever D1 holds into the caller's buffers), and the stream is drained
-    // before the error goes back: the caller may free its buffers as soon as it has it.
-    ~GateGuard() {
-      if (!word) return;
-      for (int i = 0; i < n; i++) info[i].ok = 0;
-      open();
-      hipStreamSynchronize(st);
-    }
-  } gate;
-  bool gated = h->gate_stage_b && s.gate && filtered && h->zero_copy_payload && sa == st;
-  bool cleared = false;                                  // the two clears are on the stream already
-  if (gated) {
-    if (!grid_early) launch_grid_clear(st, dp, n, s.mark);
-    launch_bin_clear(st, dp, n, s.bin_count);
-    cleared = true;
-    const uint32_t v = ++s.gate_seq;
-    if (hipStreamWaitValue32(st, s.gate, v, hipStreamWaitValueEq, 0xFFFFFFFFu) != hipSuccess) {
-      (void)hipGetLastError();                           // a runtime that reports the capability but refuses the call: this handle goes on without the gate
-      h->gate_stage_b = false; gated = false;
-    } else {
-      gate.word = s.gate; gate.value = v; gate.info = s.h_info; gate.n = n; gate.st = st;
-      const jn_status qs = queue_stage_b(list_cap + HostWorker::kCornerPoints, h->tri_cap, true, s.h_payload, 0, true);
-      if (qs != JN_OK) return qs;
-    }
-  }
-  HIP_TRY(wait_event(s.ev[EV_D2H], h->wait_spin_us));
+  *out = StageA{filtered, arranged, gpu_dt, grid_early};
+  return JN_OK;
+}
 
-  t_host0 = std::chrono::steady_clock::now();
-  size_t payload_bytes = 0;                              // frames packed back to back: one H2D copy per batch
-  if (filtered) {
+// Post-processing, raw matcher output -> D1 / D2.  When gap interpolation and adaptive mean can run as one pass (gap_mean_fusable), the
+// left image travels raw -> tmp (L/R check) -> tmp (speckle, run lists in the still idle output image) -> D1 (fused pass), so that
+// every stage reads and writes the image once; otherwise the stages run in place on D1 with tmp as scratch.
+jn_status Batch::queue_post_processing() const {
+  const bool only_left = h->p.postprocess_only_left != 0, mean = h->p.filter_adaptive_mean != 0;
+  if (h->sub) {
+    // subsampling: the matcher ran on every pixel (findMatch is per pixel, so the reference's half-size map is the full one at even
+    // (u, v)); the L/R check picks those out, everything behind it works on (W/2) x (H/2) maps with dph
+    const DevParams& dph = h->dph;
+    launch_lr_sub(st, dp, n, s.info, s.raw, j.dD1, j.dD2);
+    HIP_TRY(mark(EV_LR));
+    each_map([&](float* D) { launch_speckle(st, dph, n, s.info, D, s.label, s.size, s.tmp); });
+    HIP_TRY(mark(EV_SPECKLE));
+    each_map([&](float* D) { launch_gap(st, dph, n, s.info, D, s.tmp); });
+    HIP_TRY(mark(EV_GAP));
+    if (mean) each_map([&](float* D) { launch_adaptive_mean_sub(st, dph, n, s.info, D, s.tmp); });
+    if (h->p.filter_median) each_map([&](float* D) { launch_median(st, dph, n, s.info, D, s.tmp); });
+    HIP_TRY(mark(EV_AM));
+    return JN_OK;
+  }
+  if (fused) {
+    launch_lr_speckle(st, dp, n, s.info, s.raw, s.tmp, j.dD2, s.label, s.size, j.dD1);   // (the L/R check and the speckle pass' row labelling are one kernel here)
+    HIP_TRY(mark(EV_LR));
+    HIP_TRY(mark(EV_SPECKLE));
+    launch_gap_mean_fused(st, dp, n, s.info, s.tmp, j.dD1, mean);
+    if (!only_left) {                                    // right image: in place, fused pass into tmp, copied back
+      launch_speckle(st, dp, n, s.info, j.dD2, s.label, s.size, s.tmp);
+      launch_gap_mean_fused(st, dp, n, s.info, j.dD2, s.tmp, mean);
+      launch_copy_ok(st, dp, n, s.info, s.tmp, j.dD2);
+    }
+    HIP_TRY(mark(EV_GAP));
+  } else {
+    launch_lr_speckle(st, dp, n, s.info, s.raw, j.dD1, j.dD2, s.label, s.size, s.tmp);   // L/R check of both maps + the left map's speckle pass (its row labelling in the L/R kernel)
+    HIP_TRY(mark(EV_LR));
+    if (!only_left) launch_speckle(st, dp, n, s.info, j.dD2, s.label, s.size, s.tmp);
+    HIP_TRY(mark(EV_SPECKLE));
+    each_map([&](float* D) { launch_gap(st, dp, n, s.info, D, s.tmp); });
+    HIP_TRY(mark(EV_GAP));
+    if (mean) each_map([&](float* D) { launch_adaptive_mean(st, dp, n, s.info, D, s.tmp); });
+  }
+  if (h->p.filter_median) each_map([&](float* D) { launch_median(st, dp, n, s.info, D, s.tmp); });   // elas.cpp:133-139
+  HIP_TRY(mark(EV_AM));
+  return JN_OK;
+}
+
+// H2D copies, grid / bins / dense matching, post-processing, the scan and the attached tails, EV_END.
+jn_status Batch::queue_stage_b(const StageA& a, const StageBInput& in) const {
+  HIP_TRY(mark(EV_H2D0));
+  if (!in.device_info) HIP_TRY(hipMemcpyAsync(s.info, s.h_info, sizeof(FrameInfo) * n, hipMemcpyHostToDevice, st));
+  if (in.payload_bytes && in.payload == s.payload) HIP_TRY(hipMemcpyAsync(s.payload, s.h_payload, in.payload_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(mark(EV_H2D));
+  if (in.any_ok) {
+    if (!a.grid_early) launch_grid(st, dp, n, s.info, in.payload, 0, in.max_sup, s.mark, s.gridbits, !in.cleared);      // offsets in FrameInfo are batch-absolute
+    launch_bin(st, dp, n, s.info, s.recs, h->tri_cap, in.max_tri, s.bin_count, s.bin_list, !in.cleared, in.payload, 0);   // (forms the triangles' records on the way: k_tri_setup's work)
+    HIP_TRY(mark(EV_RASTER));
+    launch_dense(st, dp, n, s.info, s.recs, h->tri_cap, s.bin_count, s.bin_list, s.gridbits, dsrc, s.raw, false, (stage_events && h->plane_flow) ? s.ev_owner : nullptr);
+    HIP_TRY(mark(EV_DENSE));
+    const jn_status ps = queue_post_processing();
+    if (ps != JN_OK) return ps;
+  } else {
+    for (int e = EV_RASTER; e <= EV_AM; e++) HIP_TRY(mark(e));
+  }
+  if (j.scan) {
+    // the node's tail: depth map + obstacle scan of whatever D1 now holds
+    launch_scan(st, j.sp, n, j.dD1, j.dDispU8, j.dLut, dp.W, dp.H, j.dBins, j.dMeta, s.scan_scratch, j.merge ? s.d_flat : nullptr);
+    // the attached tails: the costmap of the map and the bins the scan has just written, the sub-pixel tail of the float map
+    const int native = JN_DISP_F32;
+    HIP_TRY(j.tails.launch(st, j.sp, n, j.dDispU8, j.dLut, j.dBins, j.dD1, native, dp.W, dp.H));
+  }
+  HIP_TRY(hipEventRecord(s.ev[EV_END], st));
+  return JN_OK;
+}
+
+// The most support points a frame of the slot's last kArrHist batches held: the next batch's arrangement space and LDS requests (a lone
+// sparse frame no longer shrinks them).
+void note_support_counts(Slot& s, int batch_most) {
+  s.arr_hist[s.arr_pos] = batch_most; s.arr_pos = (s.arr_pos + 1) % Slot::kArrHist;
+  s.arr_hint = *std::max_element(s.arr_hist, s.arr_hist + Slot::kArrHist);
+}
+
+// The GPU route behind stage A: stage B with capacity-sized launches, one wait, and what the host needs of the batch.
+jn_status Batch::finish_gpu_route(const StageA& a, RouteResult* out) const {
+  out->any_ok = true;
+  const jn_status qs = queue_stage_b(a, StageBInput{list_cap, h->tri_cap, true, s.payload, 0, false, true});
+  if (qs != JN_OK) return qs;
+  // what the host needs of the batch: which frames matched out (status), how many support points they held (the next launches' LDS),
+  // whether a side was handed back — copied behind everything else, read after the one wait
+  HIP_TRY(hipMemcpyAsync(s.h_info, s.info, sizeof(FrameInfo) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s.h_need, s.need_host, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(s.ev[EV_END], st));
+  HIP_TRY(wait_event(s.ev[EV_END], h->wait_spin_us));
+  HIP_TRY(hipGetLastError());
+  int batch_most = 0, handed_back = 0;
+  for (int i = 0; i < n; i++) { batch_most = std::max(batch_most, (int)s.h_info[i].reserved); handed_back |= s.h_need[i]; }   // (k_delaunay leaves the frame's support count, clipped or not, in `reserved`)
+  note_support_counts(s, batch_most);
+  out->handed_back = handed_back != 0;                   // coinciding vertices or more of them than the launch's LDS held: the whole batch again, host stage and all
+  if (!handed_back)
+    for (int i = 0; i < n; i++) if (j.status) j.status[i] = s.h_info[i].ok ? JN_OK : JN_ERR_FEW_SUPPORT;
+  return JN_OK;
+}
+
+// Latency mode: the two clears and the whole of stage B behind a shut gate, while the GPU runs stage A (see GateGuard).  *cleared: the
+// clears are on the stream, whether or not the gate could be shut behind them.
+jn_status Batch::queue_gated_stage_b(const StageA& a, GateGuard& gate, bool* cleared) const {
+  *cleared = false;
+  if (!(h->gate_stage_b && s.gate && a.filtered && h->zero_copy_payload && sa == st)) return JN_OK;
+  if (!a.grid_early) launch_grid_clear(st, dp, n, s.mark);
+  launch_bin_clear(st, dp, n, s.bin_count);
+  *cleared = true;
+  const uint32_t v = ++s.gate_seq;
+  if (hipStreamWaitValue32(st, s.gate, v, hipStreamWaitValueEq, 0xFFFFFFFFu) != hipSuccess) {
+    (void)hipGetLastError();                             // a runtime that reports the capability but refuses the call: this handle goes on without the gate
+    h->gate_stage_b = false;
+    return JN_OK;
+  }
+  gate.word = s.gate; gate.value = v; gate.info = s.h_info; gate.n = n; gate.st = st;
+  return queue_stage_b(a, StageBInput{list_cap + HostWorker::kCornerPoints, h->tri_cap, true, s.h_payload, 0, true, false});
+}
+
+// The pool's work between the two GPU stages: the triangulations of the list the device filters wrote, or filters, list and
+// triangulations from the candidates.  Fills FrameInfo and the payload in pinned memory, and the caller's status; returns what stage B
+// takes from it (the frames packed back to back: one H2D copy per batch) and, in *ms, how long it took.
+StageBInput Batch::host_stage(const StageA& a, float* ms) const {
+  StageBInput r = {};
+  const auto t0 = std::chrono::steady_clock::now();
+  if (a.filtered) {
     // the counts are known, so the frames can be placed at once and the batch is one flat set of frame-side tasks
     int batch_most = 0;
     for (int i = 0; i < n; i++) batch_most = std::max(batch_most, (int)s.h_cnt[i]);
-    s.arr_hist[s.arr_pos] = batch_most; s.arr_pos = (s.arr_pos + 1) % Slot::kArrHist;   // a lone sparse frame no longer shrinks
-    s.arr_hint = *std::max_element(s.arr_hist, s.arr_hist + Slot::kArrHist);            // the next batch's arrangement space
+    note_support_counts(s, batch_most);
     for (int i = 0; i < n; i++) {
       FrameInfo& fi = s.h_info[i];
       memset(&fi, 0, sizeof(fi));
       fi.nsup = std::min(s.h_cnt[i], list_cap) + (h->hp.add_corners ? HostWorker::kCornerPoints : 0);   // elas.cpp:435
       fi.ok = fi.nsup >= 3;                              // elas.cpp:66-71
-      payload_bytes += HostWorker::place(&fi, payload_bytes);
+      r.payload_bytes += HostWorker::place(&fi, r.payload_bytes);
     }
     // Idle pool threads (a lone pair, a few large frames) are put to work inside the triangulations: every frame side
     // is cut into 2 or 4 independent parts (delaunay.h), three short pool rounds instead of one long one.
@@ -485,7 +529,7 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
     if (want_parts == 1) {
       h->pool->run(2 * n, [&](HostWorker& w, int k) {
         const int i = k >> 1;
-        const uint16_t* arr = (arranged && s.h_arr_ok[k]) ? s.h_arr + (size_t)k * h->arr_stride : nullptr;
+        const uint16_t* arr = (a.arranged && s.h_arr_ok[k]) ? s.h_arr + (size_t)k * h->arr_stride : nullptr;
         w.triangulate_side_from_list(k & 1, s.h_list + (size_t)i * list_cap * 3, s.h_payload, &s.h_info[i], arr);
       });
     } else {
@@ -503,93 +547,137 @@ jn_status run_batch_route(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, bo
     h->pool->run(n, [&](HostWorker& w, int i) {          // phase 1: filters + support list, per frame
       w.filter_and_list(s.h_can + (size_t)i * dp.cw * dp.ch, &s.h_info[i], &s.scratch[i], false);
     });
-    for (int i = 0; i < n; i++) payload_bytes += HostWorker::place(&s.h_info[i], payload_bytes);
+    for (int i = 0; i < n; i++) r.payload_bytes += HostWorker::place(&s.h_info[i], r.payload_bytes);
     h->pool->run(2 * n, [&](HostWorker& w, int k) {      // phase 2: one triangulation per frame and side
       const int i = k >> 1;
       w.triangulate_side(k & 1, s.scratch[i], s.h_payload, &s.h_info[i]);
     });
   }
-  t_host1 = std::chrono::steady_clock::now();
-
-  int max_tri = 0, max_sup = 0;
+  *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   for (int i = 0; i < n; i++) {
     const FrameInfo& fi = s.h_info[i];
     if (j.status) j.status[i] = fi.ok ? JN_OK : JN_ERR_FEW_SUPPORT;
     if (!fi.ok) continue;
-    any_ok = 1;
-    max_tri = std::max(max_tri, std::max(fi.ntri[0], fi.ntri[1]));
-    max_sup = std::max(max_sup, fi.nsup);
+    r.any_ok = true;
+    r.max_tri = std::max(r.max_tri, std::max(fi.ntri[0], fi.ntri[1]));
+    r.max_sup = std::max(r.max_sup, fi.nsup);
   }
-  if (gated) gate.open();
+  return r;
+}
+
+// The host route behind stage A: [stage B behind the gate ->] wait for stage A -> host stage -> stage B (or the gate opens) -> wait.
+jn_status Batch::finish_host_route(const StageA& a, RouteResult* out) const {
+  GateGuard gate;
+  bool cleared = false;                                  // the two clears are on the stream already
+  const jn_status gs = queue_gated_stage_b(a, gate, &cleared);
+  if (gs != JN_OK) return gs;
+  HIP_TRY(wait_event(s.ev[EV_D2H], h->wait_spin_us));
+  StageBInput in = host_stage(a, &out->host_ms);
+  out->any_ok = in.any_ok;
+  if (gate.shut()) gate.open();
   else {
     // A latency-mode handle lets the two kernels that consume the payload read it where the host wrote it (pinned memory is visible to
     // the device): a lone pair's payload is ~50 KB read once, and the copy plus the pause behind it cost more than that (JN_ZERO_COPY=0/1).
-    const jn_status qs = queue_stage_b(max_sup, max_tri, any_ok != 0, h->zero_copy_payload ? s.h_payload : s.payload, payload_bytes, cleared);
+    in.payload = h->zero_copy_payload ? s.h_payload : s.payload; in.cleared = cleared;
+    const jn_status qs = queue_stage_b(a, in);
     if (qs != JN_OK) return qs;
   }
   HIP_TRY(wait_event(s.ev[EV_END], h->wait_spin_us));
   HIP_TRY(hipGetLastError());
-  }   // (host-stage route)
-  bool merged = false;
-  float merge_host_ms = 0.f;
-  if (j.merge) {
-    // The path's one exchange step (point_cloud.cpp:264-266 across rigs): the bins of this batch MIN-reduced over the ranks,
-    // as the batch's tail, issued by THIS worker (the submitting thread is not involved, the other slots keep the GPU busy).
-    // RCCL wants every rank to issue a communicator's collectives in one order: batches take their turn in submission order
-    // (every rank submits the same sequence), whatever order their host stages finished in.
-    // The scan is complete here (the wait above), so pack -> all-reduce -> unpack need no cross-stream dependency: chaining
-    // them to the slot's stream with events cost 0.66 ms per batch on a busy GPU (two queue hand-overs), this costs the
-    // kernels themselves plus one host wait (profiles/r03_merge_in_worker.txt).
-    const auto t_m0 = std::chrono::steady_clock::now();
-    jn_status ms_ = JN_OK;
-    if (!h->test_slot_delay_us.empty()) {                  // tests only: this slot's host side takes longer, so batches reach their merge out of submission order
-      size_t si = 0;
-      while (si < h->slots.size() && h->slots[si].get() != &s) si++;
-      const int us = h->test_slot_delay_us[si % h->test_slot_delay_us.size()];
-      if (us > 0) std::this_thread::sleep_for(std::chrono::microseconds(us));
-    }
-    {
-      std::unique_lock<std::mutex> l(h->merge_m);
-      h->merge_cv.wait(l, [&] { return h->merge_seq == j.seq; });
-      ms_ = comm_merge_async(h->comm, n, j.sp.bins, j.dBins, j.dMeta, nullptr, s.ev_merged, s.d_flat);   // packed by k_scan_finish: all-reduce in place + unpack
-      if (h->merge_log.size() >= 4096) h->merge_log.erase(h->merge_log.begin(), h->merge_log.begin() + 2048);
-      h->merge_log.push_back(j.seq);
-      h->merge_seq++;                                      // even on failure: the batches behind must not wait for ever
-    }
-    turn.done();
-    h->merge_cv.notify_all();
-    if (ms_ != JN_OK) return ms_;
-    {
-      // a short wait (two small kernels): poll tightly, a sleep's granularity would show.  Bounded: a peer that died or never issued its
-      // collective must not hang this rank — the communicator is aborted and this and all later scan batches return JN_ERR_COMM.
-      const hipError_t we = wait_event_bounded(s.ev_merged, std::max(h->wait_spin_us, 400), h->comm_timeout_ms);
-      if (we == hipErrorNotReady) { comm_abort(h->comm); return JN_ERR_COMM; }
-      HIP_TRY(we);
-      // another slot's merge timed out and aborted the communicator meanwhile: this merge's event completed because the aborted kernels
-      // exited, its bins were never reduced
-      if (comm_dead(h->comm)) return JN_ERR_COMM;
-    }
-    merge_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
-    merged = true;
-  }
-  auto t_end = std::chrono::steady_clock::now();
+  return JN_OK;
+}
 
+// One pass of the batch: stage A, then the route stage A settled on.  Returns with the batch complete on the GPU (or handed back).
+jn_status run_route(jn_elas* h, Slot& s, const Job& j, bool force_host, RouteResult* out) {
+  HIP_TRY(hipSetDevice(h->device));
+  *out = RouteResult();
+  out->t_begin = std::chrono::steady_clock::now();
+  const Batch b = plan_batch(h, s, j, force_host);
+  StageA a;
+  const jn_status qs = b.queue_stage_a(&a);
+  if (qs != JN_OK) return qs;
+  return a.gpu_dt ? b.finish_gpu_route(a, out) : b.finish_host_route(a, out);
+}
+
+// The path's one exchange step (point_cloud.cpp:264-266 across rigs): the bins of this batch MIN-reduced over the ranks,
+// as the batch's tail, issued by THIS worker (the submitting thread is not involved, the other slots keep the GPU busy).
+// RCCL wants every rank to issue a communicator's collectives in one order: batches take their turn in submission order
+// (every rank submits the same sequence), whatever order their host stages finished in.
+// The scan is complete here (the route's last wait), so pack -> all-reduce -> unpack need no cross-stream dependency: chaining
+// them to the slot's stream with events cost 0.66 ms per batch on a busy GPU (two queue hand-overs), this costs the
+// kernels themselves plus one host wait (profiles/r03_merge_in_worker.txt).
+// *host_ms: scan complete -> merged bins in place, on the worker's clock (its turn in the order included).
+jn_status merge_tail(jn_elas* h, Slot& s, const Job& j, MergeTurn& turn, float* host_ms) {
+  const auto t_m0 = std::chrono::steady_clock::now();
+  jn_status ms_ = JN_OK;
+  if (!h->test_slot_delay_us.empty()) {                  // tests only: this slot's host side takes longer, so batches reach their merge out of submission order
+    size_t si = 0;
+    while (si < h->slots.size() && h->slots[si].get() != &s) si++;
+    const int us = h->test_slot_delay_us[si % h->test_slot_delay_us.size()];
+    if (us > 0) std::this_thread::sleep_for(std::chrono::microseconds(us));
+  }
+  {
+    std::unique_lock<std::mutex> l(h->merge_m);
+    h->merge_cv.wait(l, [&] { return h->merge_seq == j.seq; });
+    ms_ = comm_merge_async(h->comm, j.n, j.sp.bins, j.dBins, j.dMeta, nullptr, s.ev_merged, s.d_flat);   // packed by k_scan_finish: all-reduce in place + unpack
+    if (h->merge_log.size() >= 4096) h->merge_log.erase(h->merge_log.begin(), h->merge_log.begin() + 2048);
+    h->merge_log.push_back(j.seq);
+    h->merge_seq++;                                      // even on failure: the batches behind must not wait for ever
+  }
+  turn.done();
+  h->merge_cv.notify_all();
+  if (ms_ != JN_OK) return ms_;
+  // a short wait (two small kernels): poll tightly, a sleep's granularity would show.  Bounded: a peer that died or never issued its
+  // collective must not hang this rank — the communicator is aborted and this and all later scan batches return JN_ERR_COMM.
+  const hipError_t we = wait_event(s.ev_merged, std::max(h->wait_spin_us, 400), h->comm_timeout_ms);
+  if (we == hipErrorNotReady) { comm_abort(h->comm); return JN_ERR_COMM; }
+  HIP_TRY(we);
+  // another slot's merge timed out and aborted the communicator meanwhile: this merge's event completed because the aborted kernels
+  // exited, its bins were never reduced
+  if (comm_dead(h->comm)) return JN_ERR_COMM;
+  *host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+  return JN_OK;
+}
+
+// The slot's record of the batch: jn_elas_last_times, _kernel_time, _merge_time, _bin_stats.
+void read_stage_times(const jn_elas* h, Slot& s, int n, const RouteResult& r, float merge_ms) {
+  const auto t_end = std::chrono::steady_clock::now();
+  const bool stage_events = h->stage_events;
   auto ms = [&](int a, int b) { float v = 0; if (stage_events) hipEventElapsedTime(&v, s.ev[a], s.ev[b]); return v; };
   jn_stage_times& t = s.times;
   t.gpu_descriptor = ms(EV_BEGIN, EV_DESC); t.gpu_support = ms(EV_DESC, EV_SUPPORT); t.d2h = ms(EV_SUPPORT, EV_D2H);
-  t.host_stage = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();
+  t.host_stage = r.host_ms;
   t.h2d = ms(EV_H2D0, EV_H2D);
   t.gpu_matching = ms(EV_H2D, EV_DENSE); t.gpu_lr = ms(EV_DENSE, EV_LR); t.gpu_speckle = ms(EV_LR, EV_SPECKLE);
   t.gpu_gap = ms(EV_SPECKLE, EV_GAP); t.gpu_adaptive_mean = ms(EV_GAP, EV_AM);
-  t.total = std::chrono::duration<float, std::milli>(t_end - t_begin).count();
+  t.total = std::chrono::duration<float, std::milli>(t_end - r.t_begin).count();
   s.last_n = n;
-  s.dense_launches = any_ok && stage_events ? 1 : 0;
+  s.dense_launches = r.any_ok && stage_events ? 1 : 0;
   if (s.dense_launches && h->plane_flow) {                   // k_bin | k_owner | k_dense_row: the matcher proper is timed from behind k_owner
     float a = 0, b = 0;
     hipEventElapsedTime(&a, s.ev[EV_RASTER], s.ev_owner); hipEventElapsedTime(&b, s.ev_owner, s.ev[EV_DENSE]);
     s.owner_ms = a; s.dense_ms = b;
   } else { s.dense_ms = ms(EV_RASTER, EV_DENSE); s.owner_ms = 0; }
-  s.merge_ms = merged ? merge_host_ms : 0.f;               // scan complete -> merged bins in place, on the worker's clock (its turn in the order included)
+  s.merge_ms = merge_ms;
+}
+
+// One batch on its slot's worker: GPU route -> (handed back ->) host route -> cross-rank merge -> stage times.
+jn_status run_batch(jn_elas* h, Slot& s, const Job& j) {
+  MergeTurn turn(h, j);
+  if (j.merge && h->test_fail_seq >= 0 && (long long)j.seq == h->test_fail_seq) return JN_ERR_INTERNAL;
+  RouteResult r;
+  jn_status e = run_route(h, s, j, false, &r);
+  if (e == JN_OK && r.handed_back) {                     // the whole batch again, host stage and all
+    s.gpu_dt_fallbacks++;
+    e = run_route(h, s, j, true, &r);
+  }
+  if (e != JN_OK) return e;
+  float merge_ms = 0.f;
+  if (j.merge) {
+    e = merge_tail(h, s, j, turn, &merge_ms);
+    if (e != JN_OK) return e;
+  }
+  read_stage_times(h, s, j.n, r, merge_ms);
   return JN_OK;
 }
 
@@ -657,9 +745,6 @@ void slot_loop(jn_elas* h, Slot* s) {
     s->cv.notify_all();
   }
 }
-
-template <typename T>
-hipError_t dmalloc(T** p, size_t count) { return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)); }
 
 }  // namespace
 
@@ -837,61 +922,56 @@ jn_status jn_elas_create(const jn_elas_params* p, int32_t W, int32_t H, int32_t 
   for (int i = 0; i < slots; i++) {
     h->slots.emplace_back(new Slot());         // owned by the handle from the start: a failure below frees it too
     Slot* s = h->slots.back().get();
-    CREATE_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    DevOwner& own = s->own;
+    CREATE_TRY(own.stream(&s->stream, hipStreamNonBlocking));
     // Measured (profiles/r03_stage_a_priority_ab.txt): with stage A prioritised the pipelined 720p bench LOSES 12 % (17.5 k
     // against 20.2 k pairs/s) — the descriptor and support kernels of one slot then push the other slots' dense kernels
     // aside, and the GPU, not the host stage, is what the pipeline waits for.  Opt-in only: JN_STAGE_A_PRIORITY=1.
     if (getenv("JN_STAGE_A_PRIORITY") && atoi(getenv("JN_STAGE_A_PRIORITY")) != 0) {
       int least = 0, greatest = 0;
       if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
-        CREATE_TRY(hipStreamCreateWithPriority(&s->stream_a, hipStreamNonBlocking, greatest));
+        CREATE_TRY(own.stream(&s->stream_a, hipStreamNonBlocking, greatest));
     }
     // blocking-sync events: the slot worker sleeps while the GPU runs instead of spinning on a core that
     // the host stage (and, on a multi-GPU node, the other ranks) could use
-    for (int e = 0; e < EV_COUNT; e++) CREATE_TRY(hipEventCreateWithFlags(&s->ev[e], hipEventBlockingSync));
-    CREATE_TRY(hipEventCreate(&s->ev_scan)); CREATE_TRY(hipEventCreate(&s->ev_merged));
-    CREATE_TRY(hipEventCreateWithFlags(&s->ev_head, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreate(&s->ev_owner));
-    CREATE_TRY(dmalloc(&s->need_host, B));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_need), B * sizeof(int32_t), hipHostMallocDefault));
+    for (int e = 0; e < EV_COUNT; e++) CREATE_TRY(own.event(&s->ev[e], hipEventBlockingSync));
+    CREATE_TRY(own.event(&s->ev_merged)); CREATE_TRY(own.event(&s->ev_head, hipEventDisableTiming)); CREATE_TRY(own.event(&s->ev_owner));
+    CREATE_TRY(own.alloc(&s->need_host, B)); CREATE_TRY(own.pinned(&s->h_need, B));
     if (h->gate_stage_b) {                                   // no signal memory: the handle simply queues stage B after the host stage
-      if (hipExtMallocWithFlags((void**)&s->gate, 8, hipMallocSignalMemory) == hipSuccess) { s->gate[0] = 0; s->gate[1] = 0; }
-      else { (void)hipGetLastError(); s->gate = nullptr; }
+      if (own.signal(&s->gate, 8) == hipSuccess) { s->gate[0] = 0; s->gate[1] = 0; }
+      else (void)hipGetLastError();
     }
-    if (h->plane_flow) CREATE_TRY(dmalloc(&s->planes, plane_bytes(W, H, 2 * (int)B) + 64));
-    else CREATE_TRY(dmalloc(&s->desc, 2 * B * px));
-    CREATE_TRY(dmalloc(&s->d_can, B * dp.cw * dp.ch));
-    CREATE_TRY(dmalloc(&s->info, B)); CREATE_TRY(dmalloc(&s->payload, B * h->payload_cap));
+    if (h->plane_flow) CREATE_TRY(own.alloc(&s->planes, plane_bytes(W, H, 2 * (int)B) + 64));
+    else CREATE_TRY(own.alloc(&s->desc, 2 * B * px));
+    CREATE_TRY(own.alloc(&s->d_can, B * dp.cw * dp.ch));
+    CREATE_TRY(own.alloc(&s->info, B)); CREATE_TRY(own.alloc(&s->payload, B * h->payload_cap));
     const size_t tiles = (size_t)((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH);
-    CREATE_TRY(dmalloc(&s->bin_count, 2 * B * tiles)); CREATE_TRY(dmalloc(&s->bin_list, 2 * B * tiles * kBinCap));
-    CREATE_TRY(dmalloc(&s->raw, 2 * B * px));
-    CREATE_TRY(dmalloc(&s->tmp, B * px)); CREATE_TRY(dmalloc(&s->label, B * px)); CREATE_TRY(dmalloc(&s->size, B * px));
-    CREATE_TRY(dmalloc(&s->scan_scratch, B * 4));
-    CREATE_TRY(dmalloc(&s->d_flat, B * (1024 + 4)));
+    CREATE_TRY(own.alloc(&s->bin_count, 2 * B * tiles)); CREATE_TRY(own.alloc(&s->bin_list, 2 * B * tiles * kBinCap));
+    CREATE_TRY(own.alloc(&s->raw, 2 * B * px));
+    CREATE_TRY(own.alloc(&s->tmp, B * px)); CREATE_TRY(own.alloc(&s->label, B * px)); CREATE_TRY(own.alloc(&s->size, B * px));
+    CREATE_TRY(own.alloc(&s->scan_scratch, B * 4));
+    CREATE_TRY(own.alloc(&s->d_flat, B * (1024 + 4)));
     const size_t grid_words = 2 * B * dp.gw * dp.gh * kGridWords;
-    CREATE_TRY(dmalloc(&s->mark, grid_words)); CREATE_TRY(dmalloc(&s->gridbits, grid_words));
-    CREATE_TRY(dmalloc(&s->recs, 2 * B * (size_t)h->tri_cap));
+    CREATE_TRY(own.alloc(&s->mark, grid_words)); CREATE_TRY(own.alloc(&s->gridbits, grid_words));
+    CREATE_TRY(own.alloc(&s->recs, 2 * B * (size_t)h->tri_cap));
     s->scratch.resize(B);
     s->sides.resize(2 * B);
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_can), B * dp.cw * dp.ch * sizeof(int16_t), hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_info), B * sizeof(FrameInfo), hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_payload), B * h->payload_cap, hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_list), B * dp.cw * dp.ch * 3 * sizeof(int16_t), hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_cnt), B * sizeof(int32_t), hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_arr), B * 2 * (size_t)h->arr_stride * sizeof(uint16_t), hipHostMallocDefault));
-    if (h->arr_stride > h->arr_cap) CREATE_TRY(hipMalloc(&s->arr_scratch, arrange_scratch_bytes((int)B, h->arr_stride)));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_arr_ok), B * 2 * sizeof(int32_t), hipHostMallocDefault));
+    CREATE_TRY(own.pinned(&s->h_can, B * dp.cw * dp.ch)); CREATE_TRY(own.pinned(&s->h_info, B)); CREATE_TRY(own.pinned(&s->h_payload, B * h->payload_cap));
+    CREATE_TRY(own.pinned(&s->h_list, B * dp.cw * dp.ch * 3)); CREATE_TRY(own.pinned(&s->h_cnt, B));
+    CREATE_TRY(own.pinned(&s->h_arr, B * 2 * (size_t)h->arr_stride));
+    if (h->arr_stride > h->arr_cap) CREATE_TRY(own.alloc_bytes(&s->arr_scratch, arrange_scratch_bytes((int)B, h->arr_stride)));
+    CREATE_TRY(own.pinned(&s->h_arr_ok, B * 2));
     if (h->gpu_delaunay) {
-      CREATE_TRY(dmalloc(&s->d_list, B * dp.cw * dp.ch * 3)); CREATE_TRY(dmalloc(&s->d_cnt, B));
-      CREATE_TRY(dmalloc(&s->d_arr, B * 2 * (size_t)h->arr_stride)); CREATE_TRY(dmalloc(&s->d_arr_ok, B * 2));
+      CREATE_TRY(own.alloc(&s->d_list, B * dp.cw * dp.ch * 3)); CREATE_TRY(own.alloc(&s->d_cnt, B));
+      CREATE_TRY(own.alloc(&s->d_arr, B * 2 * (size_t)h->arr_stride)); CREATE_TRY(own.alloc(&s->d_arr_ok, B * 2));
       CREATE_TRY(hipMemset(s->payload, 0, B * h->payload_cap));
       CREATE_TRY(hipStreamSynchronize(nullptr));             // hipMemset only queues the fill, and the slot's streams do not wait for the null stream: a late fill would wipe a payload
-      if (h->dt_gcap) CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&s->dt_scratch), delaunay_gpu_scratch_bytes((int)B, h->dt_gcap)));      // (a side k_delaunay hands back leaves its part unwritten: never uninitialised memory)
+      if (h->dt_gcap) CREATE_TRY(own.alloc(&s->dt_scratch, delaunay_gpu_scratch_bytes((int)B, h->dt_gcap)));      // (a side k_delaunay hands back leaves its part unwritten: never uninitialised memory)
     }
   }
   h->s_pitch = dp.pitch;
-  CREATE_TRY(dmalloc(&h->s_img, 2 * (size_t)H * dp.pitch));
-  CREATE_TRY(dmalloc(&h->s_D, 2 * px));
+  CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->s_img), 2 * (size_t)H * dp.pitch));
+  CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->s_D), 2 * px * sizeof(float)));
   for (auto& s : h->slots) s->th = std::thread(slot_loop, h.get(), s.get());
   *out = h.release();
   return JN_OK;
@@ -908,20 +988,8 @@ void jn_elas_destroy(jn_elas* h) {
   }
   hipSetDevice(h->device);
   for (auto& s : h->slots) {
-    hipFree(s->desc); hipFree(s->planes); hipFree(s->d_can); hipFree(s->info); hipFree(s->payload);
-    hipFree(s->bin_count); hipFree(s->bin_list); hipFree(s->raw); hipFree(s->tmp); hipFree(s->label); hipFree(s->size); hipFree(s->scan_scratch); s->tails.release(); hipFree(s->d_flat); hipFree(s->st_img); hipFree(s->st_D); hipFree(s->arr_scratch);
-    hipFree(s->mark); hipFree(s->gridbits); hipFree(s->recs);
-    hipHostFree(s->h_can); hipHostFree(s->h_info); hipHostFree(s->h_payload); hipHostFree(s->h_list); hipHostFree(s->h_cnt); hipHostFree(s->h_arr); hipHostFree(s->h_arr_ok);
-    for (int e = 0; e < EV_COUNT; e++) if (s->ev[e]) hipEventDestroy(s->ev[e]);
-    if (s->ev_scan) hipEventDestroy(s->ev_scan);
-    if (s->ev_merged) hipEventDestroy(s->ev_merged);
-    if (s->ev_head) hipEventDestroy(s->ev_head);
-    if (s->ev_owner) hipEventDestroy(s->ev_owner);
-    hipFree(s->need_host); if (s->h_need) hipHostFree(s->h_need);
-    hipFree(s->d_list); hipFree(s->d_cnt); hipFree(s->d_arr); hipFree(s->d_arr_ok); hipFree(s->dt_scratch);
-    if (s->gate) hipFree(s->gate);
-    if (s->stream_a) hipStreamDestroy(s->stream_a);
-    if (s->stream) hipStreamDestroy(s->stream);
+    hipFree(s->st_img); hipFree(s->st_D); s->tails.release();   // made after jn_elas_create: their own release (see Slot)
+    s->own.release();
   }
   hipFree(h->s_img); hipFree(h->s_D);
   h->pool.reset();

@@ -16,6 +16,7 @@
 #include "../../include/jn_subpix.h"
 #include "../../include/jn_postfilter.h"
 #include "sgm_sweep.h"
+#include "dev_owner.h"
 #include "nav_tail.h"           // kernels.h's launch_scan, and NavTails: the node's tails on a slot's stream (jn_sgm_submit_scan)
 
 namespace {
@@ -36,22 +37,81 @@ struct jn_sgm {
   int W = 0, H = 0, max_batch = 0, device = 0;
   jnav_sgm::SwDev sw = {};
   jnav_sgm::SweepSizes sizes = {};
-  jnav_sgm::SweepBuffers sb = {};
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {};
-  hipEvent_t ev_end[8] = {};   // per slot: recorded behind EVERYTHING a submit queued (sweeps + the scan tail); what jn_sgm_wait waits for
-  jn_sgm_times times = {};
-  // Pipelined form (jn_sgm_submit_scan / jn_sgm_wait): slot 0 is the set above, slots 1 .. kSgmSlots-1 get their own stream, events and
-  // buffers the first time they are used.  Batches on different slots overlap on the GPU: the upward sweep's tail (the last blocks of
-  // its parallelogram run alone) is filled by the next batch's horizontal and downward sweeps.
-  struct Extra { jnav_sgm::SweepBuffers sb = {}; hipStream_t stream = nullptr; hipEvent_t ev[4] = {}; jn_sgm_times times = {}; bool ready = false, shared = false; };
+  // One slot: its own sweep buffers, stream and events.  Slot 0 is made with the handle (jn_sgm_process_batch runs on it), the others the
+  // first time they are used (jn_sgm_submit_scan / jn_sgm_wait).  Batches on different slots overlap on the GPU: the upward sweep's tail
+  // (the last blocks of its parallelogram run alone) is filled by the next batch's horizontal and downward sweeps.
+  // Everything below except the tails' scratch (NavTails::release) and the buffers' side stream (sweep_release) belongs to `own`.
+  struct Slot {
+    jnav::DevOwner own;
+    jnav_sgm::SweepBuffers sb = {};
+    hipStream_t stream = nullptr;               // its own, or with JN_SGM_STREAMS a lower slot's (`shared`: not in `own`)
+    hipEvent_t ev[4] = {};
+    hipEvent_t ev_end = nullptr;                // recorded behind EVERYTHING a submit queued (sweeps + the scan tail); what jn_sgm_wait waits for
+    unsigned long long* scan_scratch = nullptr; // [max_batch][4], the scan tail's extrema (made by the first scan batch)
+    bool ready = false, shared = false, pending = false;
+    jnav::NavTails tails;                       // what jn_sgm_attach_costmap / _subpix / _postfilter attached to the slot's scan batches
+  };
   enum { kSgmSlots = 8 };
-  Extra extra[kSgmSlots - 1];
-  unsigned long long* scan_scratch[kSgmSlots] = {};   // [max_batch][4] per slot, the scan tail's extrema
-  bool pending[kSgmSlots] = {};
-  jnav::NavTails tails[kSgmSlots];    // what jn_sgm_attach_costmap / jn_sgm_attach_subpix attached to each slot's scan batches
-  static_assert(kSgmSlots == sizeof(ev_end) / sizeof(ev_end[0]), "one end event per slot");
+  Slot slots[kSgmSlots];
+  jn_sgm_times times = {};                      // of the batch waited for last (jn_sgm_last_times)
+  __attribute__((visibility("hidden"))) ~jn_sgm() = default;   // (not trivial any more; the library exports its C ABI only)
 };
+
+static jn_status sgm_make_slot(jn_sgm* h, int slot);
+
+// What sgm_make_slot makes; a failure returns half-way and leaves the release to it.
+static jn_status sgm_slot_resources(jn_sgm* h, int slot) {
+  jn_sgm::Slot& s = h->slots[slot];
+  const jnav_sgm::SweepSizes& z = h->sizes;
+  HIP_TRY(s.own.alloc(&s.sb.gm, z.gm));
+  HIP_TRY(s.own.alloc(&s.sb.volF, z.vol * (h->sw.wide ? 2 : 1)));
+  HIP_TRY(s.own.alloc(&s.sb.volH0, z.vol));
+  HIP_TRY(s.own.alloc(&s.sb.volH1, z.vol));
+  HIP_TRY(s.own.alloc_bytes(reinterpret_cast<void**>(&s.sb.gx), z.gx));
+  s.sb.gx_bytes = z.gx;
+  if (slot != 0) s.sb.epoch = h->slots[0].sb.epoch;
+  else if (const char* e = JN_HOOK_ENV("JN_SGM_EPOCH_START")) s.sb.epoch = (uint32_t)atoi(e) & 0xFFFFu;   // test hook: start next to the tag's wrap-around
+  HIP_TRY(s.own.alloc_bytes(reinterpret_cast<void**>(&s.sb.flags), z.flags));
+  HIP_TRY(s.own.alloc_bytes(reinterpret_cast<void**>(&s.sb.minr), z.minr));
+  HIP_TRY(s.own.alloc_bytes(reinterpret_cast<void**>(&s.sb.dl), z.dl));
+  static const int share = getenv("JN_SGM_STREAMS") ? atoi(getenv("JN_SGM_STREAMS")) : 0;     // experiment: slot s queues on the stream of slot s % share
+  if (share > 0 && slot >= share) {
+    const int lower = slot % share;
+    const jn_status el = sgm_make_slot(h, lower);
+    if (el != JN_OK) return el;
+    s.stream = h->slots[lower].stream; s.shared = true;
+  } else HIP_TRY(s.own.stream(&s.stream, hipStreamNonBlocking));
+  // tag 0 = "never written" (sgm_sweep.hip, k_sw_w).  On the stream the sweeps run on, ahead of the slot's first sweep: hipMemset returns
+  // once the fill is QUEUED on the null stream, which a non-blocking stream does not wait for — a fill that runs late wipes columns a
+  // block is still waiting to read.
+  HIP_TRY(hipMemsetAsync(s.sb.gx, 0, s.sb.gx_bytes, s.stream));
+  for (auto& e : s.ev) HIP_TRY(s.own.event(&e));
+  return JN_OK;
+}
+
+// A slot's buffers, stream and events, made once.  A slot that fails half-way gives back what it made and stays not ready.
+static jn_status sgm_make_slot(jn_sgm* h, int slot) {
+  jn_sgm::Slot& s = h->slots[slot];
+  if (s.ready) return JN_OK;
+  const jn_status e = sgm_slot_resources(h, slot);
+  if (e != JN_OK) {
+    s.own.release();
+    s.sb = {}; s.stream = nullptr; s.shared = false;
+    for (auto& v : s.ev) v = nullptr;
+    return e;
+  }
+  s.ready = true;
+  return JN_OK;
+}
+
+// The stage times of the slot's last batch, once it is complete.
+static void sgm_read_times(jn_sgm* h, const jn_sgm::Slot& s) {
+  jn_sgm_times& t = h->times;
+  hipEventElapsedTime(&t.prefilter, s.ev[0], s.ev[1]);
+  hipEventElapsedTime(&t.paths, s.ev[1], s.ev[2]);
+  hipEventElapsedTime(&t.wta, s.ev[2], s.ev[3]);
+  hipEventElapsedTime(&t.total, s.ev[0], s.ev[3]);
+}
 
 extern "C" {
 
@@ -62,21 +122,12 @@ void jn_sgm_params_default(jn_sgm_params* p) {
 void jn_sgm_destroy(jn_sgm* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (auto& x : h->extra) {
-    if (x.stream && !x.shared) hipStreamSynchronize(x.stream);
-    jnav_sgm::sweep_release(x.sb);
-    hipFree(x.sb.gm); hipFree(x.sb.volF); hipFree(x.sb.volH0); hipFree(x.sb.volH1); hipFree(x.sb.gx); hipFree(x.sb.flags); hipFree(x.sb.minr); hipFree(x.sb.dl);
-    for (auto& e : x.ev) if (e) hipEventDestroy(e);
-    if (x.stream && !x.shared) hipStreamDestroy(x.stream);
+  for (auto& s : h->slots) if (s.stream && !s.shared) hipStreamSynchronize(s.stream);   // (a shared stream: once, by the slot that made it)
+  for (auto& s : h->slots) {
+    jnav_sgm::sweep_release(s.sb);
+    s.tails.release();
+    s.own.release();
   }
-  for (auto& q : h->scan_scratch) hipFree(q);
-  for (auto& t : h->tails) t.release();
-  jnav_sgm::sweep_release(h->sb);
-  hipFree(h->sb.gm); hipFree(h->sb.volF); hipFree(h->sb.volH0); hipFree(h->sb.volH1); hipFree(h->sb.gx); hipFree(h->sb.flags); hipFree(h->sb.minr); hipFree(h->sb.dl);
-  for (auto& e : h->ev) if (e) hipEventDestroy(e);
-  for (auto& e : h->ev_end) if (e) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
   delete h;
 }
 
@@ -92,74 +143,22 @@ jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t ma
   HIP_TRY(hipSetDevice(device));
   jn_sgm* h = new jn_sgm();
   h->p = *p; h->W = W; h->H = H; h->max_batch = max_batch; h->device = device;
-#define SGM_CREATE_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { fprintf(stderr, "libjn_stereo: %s failed: %s\n", #expr, hipGetErrorString(e__)); jn_sgm_destroy(h); return JN_ERR_NO_DEVICE; } } while (0)
-  {
-    jnav_sgm::SweepSizes& z = h->sizes;
-    jnav_sgm::sweep_geometry(W, H, D, p->P1, p->P2, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->sw, &z, max_batch);
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.gm), z.gm));
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.volF), z.vol * (h->sw.wide ? 2 : 1)));
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.volH0), z.vol));
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.volH1), z.vol));
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.gx), z.gx));
-    h->sb.gx_bytes = z.gx;
-    if (const char* e = JN_HOOK_ENV("JN_SGM_EPOCH_START")) h->sb.epoch = (uint32_t)atoi(e) & 0xFFFFu;   // test hook: start next to the tag's wrap-around
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.flags), z.flags));
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.minr), z.minr));
-    SGM_CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->sb.dl), z.dl));
-  }
-  SGM_CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  // tag 0 = "never written" (sgm_sweep.hip, k_sw_w).  On the stream the sweeps run on: hipMemset returns once the fill is QUEUED on the null
-  // stream, which a non-blocking stream does not wait for — a fill that runs late wipes columns a block is still waiting to read.
-  SGM_CREATE_TRY(hipMemsetAsync(h->sb.gx, 0, h->sb.gx_bytes, h->stream));
-  for (auto& e : h->ev) SGM_CREATE_TRY(hipEventCreate(&e));
-#undef SGM_CREATE_TRY
+  jnav_sgm::sweep_geometry(W, H, D, p->P1, p->P2, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->sw, &h->sizes, max_batch);
+  const jn_status e = sgm_make_slot(h, 0);
+  if (e != JN_OK) { jn_sgm_destroy(h); return e; }
   *out = h;
   return JN_OK;
 }
 
 jn_status jn_sgm_process_batch(jn_sgm* h, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride, int16_t* dDisp) {
   if (!h || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dDisp || pitch < h->W) return JN_ERR_INVALID;
-  if (h->pending[0]) return JN_ERR_INVALID;                     // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
+  jn_sgm::Slot& s = h->slots[0];
+  if (s.pending) return JN_ERR_INVALID;                         // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
   HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, h->sb, h->ev, true));
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, s.stream, s.sb, s.ev, true));
+  HIP_TRY(hipStreamSynchronize(s.stream));
   HIP_TRY(hipGetLastError());
-  hipEventElapsedTime(&h->times.prefilter, h->ev[0], h->ev[1]);
-  hipEventElapsedTime(&h->times.paths, h->ev[1], h->ev[2]);
-  hipEventElapsedTime(&h->times.wta, h->ev[2], h->ev[3]);
-  hipEventElapsedTime(&h->times.total, h->ev[0], h->ev[3]);
-  return JN_OK;
-}
-
-// A slot beyond the first: its own buffers, stream and events, allocated when it is first used.
-static jn_status sgm_ensure_slot(jn_sgm* h, int slot) {
-  if (slot == 0) return JN_OK;
-  jn_sgm::Extra& x = h->extra[slot - 1];
-  if (x.ready) return JN_OK;
-  const jnav_sgm::SweepSizes& z = h->sizes;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gm), z.gm));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volF), z.vol * (h->sw.wide ? 2 : 1)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH0), z.vol));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.volH1), z.vol));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.gx), z.gx));
-  x.sb.gx_bytes = z.gx;
-  x.sb.epoch = h->sb.epoch;                                     // (tests start it next to the tag's wrap-around)
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.flags), z.flags));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.minr), z.minr));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.sb.dl), z.dl));
-  {
-    static const int share = getenv("JN_SGM_STREAMS") ? atoi(getenv("JN_SGM_STREAMS")) : 0;     // experiment: slot s queues on the stream of slot s % share
-    if (share > 0 && slot >= share) {
-      const int lower = slot % share;
-      const jn_status el = sgm_ensure_slot(h, lower);
-      if (el != JN_OK) return el;
-      x.stream = lower == 0 ? h->stream : h->extra[lower - 1].stream; x.shared = true;
-    } else HIP_TRY(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
-  }
-  HIP_TRY(hipMemsetAsync(x.sb.gx, 0, x.sb.gx_bytes, x.stream)); // ahead of the slot's first sweep in stream order (see jn_sgm_create)
-  for (auto& e : x.ev) HIP_TRY(hipEventCreate(&e));
-  x.ready = true;
+  sgm_read_times(h, s);
   return JN_OK;
 }
 
@@ -167,85 +166,81 @@ jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* 
                              const jn_scan_params* sp, const uint8_t* dLut, uint8_t* dDispU8, double* dBins, double* dMeta) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dDisp || pitch < h->W) return JN_ERR_INVALID;
   if (sp && (!dLut || !dDispU8 || !dBins || !dMeta || sp->bins < 1 || sp->bins > 1024)) return JN_ERR_INVALID;
-  if (h->pending[slot]) return JN_ERR_INVALID;                  // one batch per slot: jn_sgm_wait first
+  jn_sgm::Slot& s = h->slots[slot];
+  if (s.pending) return JN_ERR_INVALID;                         // one batch per slot: jn_sgm_wait first
   HIP_TRY(hipSetDevice(h->device));
-  const jn_status es = sgm_ensure_slot(h, slot);
+  const jn_status es = sgm_make_slot(h, slot);
   if (es != JN_OK) return es;
-  if (sp && !h->scan_scratch[slot]) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->scan_scratch[slot]), sizeof(unsigned long long) * 4 * h->max_batch));
-  jnav_sgm::SweepBuffers& sb = slot == 0 ? h->sb : h->extra[slot - 1].sb;
-  hipStream_t st = slot == 0 ? h->stream : h->extra[slot - 1].stream;
-  hipEvent_t* ev = slot == 0 ? h->ev : h->extra[slot - 1].ev;
+  if (sp && !s.scan_scratch) HIP_TRY(s.own.alloc(&s.scan_scratch, (size_t)4 * h->max_batch));
+  jnav_sgm::SweepBuffers& sb = s.sb;
+  hipStream_t st = s.stream;
   // With a scan: ONE tail kernel applies the L/R check, writes the int16 map and the mono8 map (point_cloud.cpp:422 semantics) and scans
   // (JN_SGM_TAIL=3: the three kernels k_sw_lr, k_sgm_to_u8, k_scan one after the other, for A/B).
   static const bool fused_tail = !(getenv("JN_SGM_TAIL") && atoi(getenv("JN_SGM_TAIL")) == 3);
   // An attached post-filter (include/jn_postfilter.h) sits between the L/R check and everything that reads the map, so the one-kernel tail
   // cannot be used: such a slot queues the three kernels, with the filter in place on dDisp behind the first.
-  const jnav::NavTails& tails = h->tails[slot];
+  const jnav::NavTails& tails = s.tails;
   const bool fuse = sp && fused_tail && !tails.pf.on;
-  HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, sb, ev, false, !fuse));
+  HIP_TRY(jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, (long long)image_stride, dDisp, st, sb, s.ev, false, !fuse));
   HIP_TRY(tails.launch_postfilter_in_place(st, n, dDisp, h->W, h->H));
   if (fuse) {
     jnav::SgmWinners w;
     w.dl = sb.dl; w.minr = sb.minr; w.disp = dDisp; w.lr = h->sw.lr; w.subpixel = h->sw.subpixel;
-    jnav::launch_scan(st, *sp, n, nullptr, dDispU8, dLut, h->W, h->H, dBins, dMeta, h->scan_scratch[slot], nullptr, &w);
+    jnav::launch_scan(st, *sp, n, nullptr, dDispU8, dLut, h->W, h->H, dBins, dMeta, s.scan_scratch, nullptr, &w);
   } else if (sp) {
     const long long px = (long long)n * h->W * h->H;
     hipLaunchKernelGGL(k_sgm_to_u8, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, dDisp, h->p.subpixel ? 1 : 0, dDispU8, px);
-    jnav::launch_scan(st, *sp, n, nullptr, dDispU8, dLut, h->W, h->H, dBins, dMeta, h->scan_scratch[slot]);
+    jnav::launch_scan(st, *sp, n, nullptr, dDispU8, dLut, h->W, h->H, dBins, dMeta, s.scan_scratch);
   }
   if (sp) {                                                     // the attached tails: the costmap of the mono8 map and the bins just written, the sub-pixel tail of the int16 map
     const int native = h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16;
     HIP_TRY(tails.launch(st, *sp, n, dDispU8, dLut, dBins, dDisp, native, h->W, h->H));
   }
   // the batch's end: behind the scan tail, not behind the sweeps (ev[3] stays the end of the winner-takes-all timing)
-  if (!h->ev_end[slot]) HIP_TRY(hipEventCreateWithFlags(&h->ev_end[slot], hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->ev_end[slot], st));
+  if (!s.ev_end) HIP_TRY(s.own.event(&s.ev_end, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(s.ev_end, st));
   HIP_TRY(hipGetLastError());
-  h->pending[slot] = true;
+  s.pending = true;
   return JN_OK;
 }
 
 jn_status jn_sgm_attach_costmap(jn_sgm* h, int32_t slot, const jn_costmap_params* cp, uint16_t* dHits, int8_t* dGrid) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
-  if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
-  return h->tails[slot].attach_costmap(h->device, h->max_batch, cp, dHits, dGrid);
+  if (h->slots[slot].pending) return JN_ERR_INVALID;            // a batch is in flight on the slot: jn_sgm_wait first
+  return h->slots[slot].tails.attach_costmap(h->device, h->max_batch, cp, dHits, dGrid);
 }
 
 jn_status jn_sgm_attach_subpix(jn_sgm* h, int32_t slot, const jn_costmap_params* cp, double* dBins, double* dMeta, uint16_t* dHits, int8_t* dGrid) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
-  if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
-  return h->tails[slot].attach_subpix(h->device, h->max_batch, cp, dBins, dMeta, dHits, dGrid);
+  if (h->slots[slot].pending) return JN_ERR_INVALID;            // a batch is in flight on the slot: jn_sgm_wait first
+  return h->slots[slot].tails.attach_subpix(h->device, h->max_batch, cp, dBins, dMeta, dHits, dGrid);
 }
 
 jn_status jn_sgm_attach_postfilter(jn_sgm* h, int32_t slot, const jn_postfilter_params* fp, uint32_t* dStats) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
-  if (h->pending[slot]) return JN_ERR_INVALID;                  // a batch is in flight on the slot: jn_sgm_wait first
-  return h->tails[slot].attach_postfilter(h->device, h->max_batch, h->W, h->H, h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16, fp, dStats);
+  if (h->slots[slot].pending) return JN_ERR_INVALID;            // a batch is in flight on the slot: jn_sgm_wait first
+  return h->slots[slot].tails.attach_postfilter(h->device, h->max_batch, h->W, h->H, h->p.subpixel ? JN_DISP_I16_SUB : JN_DISP_I16, fp, dStats);
 }
 
 jn_status jn_sgm_wait(jn_sgm* h, int32_t slot) {
   if (!h || slot < 0 || slot >= jn_sgm::kSgmSlots) return JN_ERR_INVALID;
-  if (!h->pending[slot]) return JN_OK;
+  jn_sgm::Slot& s = h->slots[slot];
+  if (!s.pending) return JN_OK;
   HIP_TRY(hipSetDevice(h->device));
-  hipEvent_t* ev = slot == 0 ? h->ev : h->extra[slot - 1].ev;
-  jn_sgm_times& t = slot == 0 ? h->times : h->extra[slot - 1].times;
-  h->pending[slot] = false;
-  HIP_TRY(hipEventSynchronize(h->ev_end[slot]));                // the slot's own end, scan tail included (its stream may carry a later slot's batch)
+  s.pending = false;
+  HIP_TRY(hipEventSynchronize(s.ev_end));                       // the slot's own end, scan tail included (its stream may carry a later slot's batch)
   HIP_TRY(hipGetLastError());
-  hipEventElapsedTime(&t.prefilter, ev[0], ev[1]);
-  hipEventElapsedTime(&t.paths, ev[1], ev[2]);
-  hipEventElapsedTime(&t.wta, ev[2], ev[3]);
-  hipEventElapsedTime(&t.total, ev[0], ev[3]);
-  if (slot != 0) h->times = t;                                  // jn_sgm_last_times: the batch waited for last
+  sgm_read_times(h, s);
   return JN_OK;
 }
 
 const void* jn_sgm_debug_ptr(jn_sgm* h, int32_t which, int32_t info[5]) {
   if (!h) return nullptr;
   if (info) { info[0] = h->sw.wide; info[1] = h->sw.Wp; info[2] = h->sw.padl; info[3] = h->sw.NB; info[4] = 1; }
+  const jnav_sgm::SweepBuffers& sb = h->slots[0].sb;
   switch (which) {
-    case 0: return h->sb.volF; case 1: return h->sb.volH0; case 2: return h->sb.volH1;
-    case 3: return h->sb.minr; case 4: return h->sb.dl; case 5: return h->sb.gm;
+    case 0: return sb.volF; case 1: return sb.volH0; case 2: return sb.volH1;
+    case 3: return sb.minr; case 4: return sb.dl; case 5: return sb.gm;
   }
   return nullptr;
 }
