@@ -8,7 +8,7 @@ compute lives in csrc/.  Importing the compute API requires the built library; t
 from ._lib import load, hooks_library, JnError, ElasParams, ScanParams, EXPORTS, LIB_PATH, HOOKS_LIB_PATH  # noqa: F401
 from .elas import Elas  # noqa: F401
 from . import node, device, parallel, navigate  # noqa: F401
-from .sgm import Sgm, SGM_EXPORTS  # noqa: F401
+from .sgm import Sgm, SgmCostParams, SGM_EXPORTS, SGM_COST_EXPORTS  # noqa: F401
 from .bm import Bm, BM_EXPORTS  # noqa: F401
 from . import costmap  # noqa: F401
 from .costmap import CostmapParams, COSTMAP_EXPORTS  # noqa: F401

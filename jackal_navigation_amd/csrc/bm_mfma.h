@@ -20,4 +20,10 @@ void geometry(int W, int H, int D, int r, int cap, int lr, int subpixel, QDev* s
 hipError_t run(const QDev& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, uint8_t* g, int32_t* Q, uint32_t* keysL, uint32_t* keysR,
                int16_t* dDisp, uint8_t* dU8, hipStream_t st, hipEvent_t* ev);
 
+// The SGM mode's block-SSD cost volume (include/jn_sgm_cost.h): prefilter, squared patch norms and the left-referenced pass with
+// min(SSD >> cost_shift, cost_max) of every pair 0 <= x - u < D as a byte of cost [n][H][W][D] (16-byte aligned) in place of a winner.
+// s.D is 64, 128 or 256; g and Q are geometry()'s buffers.
+hipError_t cost_volume(const QDev& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, uint8_t* g, int32_t* Q, int cost_shift, int cost_max,
+                       uint8_t* cost, hipStream_t st);
+
 }  // namespace jnav_bmq

@@ -110,16 +110,24 @@ DEV uint32_t neg_bytes(uint32_t x) { return (0x80808080u - x) ^ 0x80808080u; }
 
 // ---- matching: one side.  SIDE 0: reference columns x of the left image against u = x - d of the right one; SIDE 1: reference columns u
 // of the right image against x = u + d of the left one.  keys: [n][H][W] uint32 (cost << 8 | d). ----
-template <int NT, int R, int SIDE>
-__global__ void __launch_bounds__(256, 2) k_bmq_match(QDev s, int n, int band, const uint8_t* __restrict__ g, const int32_t* __restrict__ Q,
-                                                   uint32_t* __restrict__ keys_out) {
+// The body of the matching pass up to the accumulators, and what becomes of them.  VOL = false: keys and the winner (k_bmq_match).
+// VOL = true (SIDE 0 only; k_sgc_volume, include/jn_sgm_cost.h): every pair of the band leaves as a byte, min(SSD >> cost_shift, cost_max),
+// into cost_out [n][H][W][D].  A lane holds one column x and 16 candidate columns of a tile: runs of four consecutive d, and the 32 lanes'
+// bytes belong to 32 different pixels.  They are transposed through a wave-private LDS tile [32 columns][D + 64] (one ds_write_b8 per pair at a
+// compile-time offset from a per-lane base: no address arithmetic, and the pairs outside the band land in the 32 bytes either side of a
+// column's D), from which the wave writes the 32 D CONTIGUOUS bytes of its 32 pixels as 16-byte pieces, 1 KB per store instruction.
+template <int NT> struct VolTile { static constexpr int STR = 32 * NT + 32; };     // bytes per column of the transposition tile: D + 64
+template <int NT, int R, int SIDE, bool VOL>
+DEV void match_body(QDev s, int n, int band, const uint8_t* __restrict__ g, const int32_t* __restrict__ Q, uint32_t* __restrict__ keys_out,
+                    uint8_t* __restrict__ cost_out, int cost_shift, int cost_max) {
   constexpr int TAPS = 2 * R + 1, RING = 2 * R + 2;
   constexpr int WAD = 8 * NT + 8;                               // dwords of an A-side row: 4 bytes ahead of the first tile, 32 NT columns, 4 + 12 behind, rounded up
   constexpr int WBD = 16;                                       // dwords of a B-side row: 4 + 32 + 4 + 12, rounded up
   constexpr int NLD = (WAD + WBD + 63) / 64;                    // image dwords a lane fetches per row
   constexpr int NQL = (32 * NT + 63) / 64;                      // key halves of the A side a lane fetches per row
-  constexpr int WAVE_DW = RING * (2 * WAD + WBD) + WAD + WBD + 32 * NT;
-  extern __shared__ uint32_t lds[];
+  constexpr int STR = VolTile<NT>::STR;
+  constexpr int WAVE_DW = RING * (2 * WAD + WBD) + WAD + WBD + 32 * NT + (VOL ? 8 * STR : 0);    // (every term is a multiple of 4: the tile is 16-byte aligned)
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5, c = lane & 31;
   const int x0 = (blockIdx.x * 4 + wave) * 32, y0 = blockIdx.y * band, img = blockIdx.z;
@@ -208,6 +216,36 @@ __global__ void __launch_bounds__(256, 2) k_bmq_match(QDev s, int n, int band, c
     fetch_keys(y + 1);
     const bool first = y == y0;
     step(aneg + slot_new * WAD, bb + slot_new * WBD, first ? azero : apos + slot_old * WAD, first ? azero + WAD : bb + slot_old * WBD);
+    if constexpr (VOL) {
+      // 256 SSD + d = (-X << 9) + QR(u) + QL(x); row i = 8 gq + 4 h + k of tile t is disparity c + 32 (NT-1-t) - i, stored at byte 32 + d of
+      // column c: every pair of every tile has a byte of its own inside the column's D + 64
+      uint8_t* tile = reinterpret_cast<uint8_t*>(qrow + 32 * NT);
+      uint8_t* wr = tile + c * (STR + 1) - 4 * h;
+      const uint32_t sh = 8u + (uint32_t)cost_shift, cmax = (uint32_t)cost_max;
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int gq = 0; gq < 4; gq++) {
+          const int4 q4 = *reinterpret_cast<const int4*>(qrow + 32 * t + 8 * gq + 4 * h);
+          const uint32_t qv[4] = {(uint32_t)q4.x, (uint32_t)q4.y, (uint32_t)q4.z, (uint32_t)q4.w};
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            const uint32_t val = ((uint32_t)acc[t][4 * gq + k] << 9) + qv[k] + (uint32_t)p_here;
+            wr[32 * (NT - t) - 8 * gq - k] = (uint8_t)min(val >> sh, cmax);
+          }
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+      constexpr int PPC = 2 * (NT - 1);                          // 16-byte pieces per pixel
+      uint8_t* orow = cost_out + (((size_t)img * s.H + y) * s.W + x0) * (size_t)(32 * (NT - 1));
+#pragma unroll
+      for (int k = 0; k < NT - 1; k++) {
+        const int pi = lane + 64 * k, cc = pi / PPC, pc = pi - cc * PPC;
+        const uint4 v = *reinterpret_cast<const uint4*>(tile + cc * STR + 32 + 16 * pc);
+        if (x0 + cc < s.W) *reinterpret_cast<uint4*>(orow + 16 * pi) = v;
+      }
+    } else {
     // ---- winner: min over the band of (-X << 9) + key half; in-lane over the 16 rows of every tile, then across the two half-waves ----
     int32_t m = 0x7FFFFFFF, v0[16];
 #pragma unroll
@@ -243,9 +281,22 @@ __global__ void __launch_bounds__(256, 2) k_bmq_match(QDev s, int n, int band, c
       m = min((int32_t)sw[0], (int32_t)sw[1]);
     }
     if (h == 0 && x0 + c < s.W) keys_out[((size_t)img * s.H + y) * s.W + x0 + c] = (uint32_t)(m + p_here);
+    }
     slot_new = slot_new + 1 == RING ? 0 : slot_new + 1;
     slot_old = slot_old + 1 == RING ? 0 : slot_old + 1;
   }
+}
+
+template <int NT, int R, int SIDE>
+__global__ void __launch_bounds__(256, 2) k_bmq_match(QDev s, int n, int band, const uint8_t* __restrict__ g, const int32_t* __restrict__ Q,
+                                                   uint32_t* __restrict__ keys_out) {
+  match_body<NT, R, SIDE, false>(s, n, band, g, Q, keys_out, nullptr, 0, 0);
+}
+// the block-SSD cost volume of the SGM mode (include/jn_sgm_cost.h): the left-referenced pass with bytes in place of a winner
+template <int NT, int R>
+__global__ void __launch_bounds__(256, 2) k_sgc_volume(QDev s, int n, int band, const uint8_t* __restrict__ g, const int32_t* __restrict__ Q,
+                                                    uint8_t* __restrict__ cost_out, int cost_shift, int cost_max) {
+  match_body<NT, R, 0, true>(s, n, band, g, Q, nullptr, cost_out, cost_shift, cost_max);
 }
 
 // ---- L/R check and output; with the sub-pixel option the two costs next to the winner straight from their definition:
@@ -346,6 +397,54 @@ static hipError_t launch_match_any(hipStream_t st, const QDev& s, int n, int ban
   }
 }
 
+static int band_rows(const QDev& s, int n) {
+  // rows per wave: long bands amortise the 2r rows of warm-up, short ones fill the GPU when the batch is small (a lone pair)
+  int band = 96;
+  const long long tiles = (long long)((s.W + 31) / 32) * n;
+  while (band > 12 && tiles * ((s.H + band - 1) / band) < 8192) band = (band + 1) / 2;
+  if (const char* env = JN_HOOK_ENV("JN_BMQ_BAND")) band = std::min(std::max(atoi(env), 1), 1024);
+  return band;
+}
+
+template <int NT, int R>
+static hipError_t launch_volume(hipStream_t st, const QDev& s, int n, int band, const uint8_t* g, const int32_t* Q, uint8_t* cost, int cost_shift, int cost_max) {
+  constexpr int RING = 2 * R + 2, WAD = 8 * NT + 8, WBD = 16, WAVE_DW = RING * (2 * WAD + WBD) + WAD + WBD + 32 * NT + 8 * VolTile<NT>::STR;
+  const size_t ldsb = (size_t)4 * WAVE_DW * sizeof(uint32_t);
+  if (ldsb > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sgc_volume<NT, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid(((s.W + 31) / 32 + 3) / 4, (s.H + band - 1) / band, n);
+  hipLaunchKernelGGL((k_sgc_volume<NT, R>), grid, dim3(256), ldsb, st, s, n, band, g, Q, cost, cost_shift, cost_max);
+  return hipGetLastError();
+}
+template <int R>
+static hipError_t launch_volume_r(hipStream_t st, const QDev& s, int n, int band, const uint8_t* g, const int32_t* Q, uint8_t* cost, int cost_shift, int cost_max) {
+  switch (s.NT) {                                                // D = 64, 128, 256: what the SGM sweeps take
+    case 3: return launch_volume<3, R>(st, s, n, band, g, Q, cost, cost_shift, cost_max);
+    case 5: return launch_volume<5, R>(st, s, n, band, g, Q, cost, cost_shift, cost_max);
+    case 9: return launch_volume<9, R>(st, s, n, band, g, Q, cost, cost_shift, cost_max);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t cost_volume(const QDev& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, uint8_t* g, int32_t* Q, int cost_shift, int cost_max,
+                       uint8_t* cost, hipStream_t st) {
+  hipLaunchKernelGGL(k_bmq_prefilter, dim3((s.Wp / 4 + 255) / 256, s.H, 2 * n), dim3(256), 0, st, s, dI1, dI2, pitch, stride, n, g);
+  const dim3 bgrid((s.Wp + 255) / 256, (s.H + kBoxBand - 1) / kBoxBand, 2 * n);
+  switch (s.r) {
+    case 2: hipLaunchKernelGGL(k_bmq_box<2>, bgrid, dim3(256), 0, st, s, n, g, Q); break;
+    case 3: hipLaunchKernelGGL(k_bmq_box<3>, bgrid, dim3(256), 0, st, s, n, g, Q); break;
+    default: hipLaunchKernelGGL(k_bmq_box<4>, bgrid, dim3(256), 0, st, s, n, g, Q); break;
+  }
+  const int band = band_rows(s, n);
+  switch (s.r) {
+    case 2: return launch_volume_r<2>(st, s, n, band, g, Q, cost, cost_shift, cost_max);
+    case 3: return launch_volume_r<3>(st, s, n, band, g, Q, cost, cost_shift, cost_max);
+    default: return launch_volume_r<4>(st, s, n, band, g, Q, cost, cost_shift, cost_max);
+  }
+}
+
 hipError_t run(const QDev& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, uint8_t* g, int32_t* Q, uint32_t* keysL, uint32_t* keysR,
                int16_t* dDisp, uint8_t* dU8, hipStream_t st, hipEvent_t* ev) {
   hipError_t e;
@@ -357,11 +456,7 @@ hipError_t run(const QDev& s, int n, const uint8_t* dI1, const uint8_t* dI2, int
     default: hipLaunchKernelGGL(k_bmq_box<4>, bgrid, dim3(256), 0, st, s, n, g, Q); break;
   }
   if ((e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
-  // rows per wave: long bands amortise the 2r rows of warm-up, short ones fill the GPU when the batch is small (a lone pair)
-  int band = 96;
-  const long long tiles = (long long)((s.W + 31) / 32) * n;
-  while (band > 12 && tiles * ((s.H + band - 1) / band) < 8192) band = (band + 1) / 2;
-  if (const char* env = JN_HOOK_ENV("JN_BMQ_BAND")) band = std::min(std::max(atoi(env), 1), 1024);
+  const int band = band_rows(s, n);
   if ((e = launch_match_any<0>(st, s, n, band, g, Q, keysL)) != hipSuccess) return e;
   if (s.lr >= 0 && (e = launch_match_any<1>(st, s, n, band, g, Q, keysR)) != hipSuccess) return e;
   if ((e = hipEventRecord(ev[2], st)) != hipSuccess) return e;

@@ -46,4 +46,11 @@ void sweep_geometry(int W, int H, int D, int P1, int P2, int cap, int lr, int su
 hipError_t sweep_run(const SwDev& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, int16_t* dDisp, hipStream_t st,
                      SweepBuffers& b, hipEvent_t* ev, bool side_overlap, bool lr_kernel = true);
 
+// The same sweeps over a byte cost volume (include/jn_sgm_cost.h): cost [n][H][W][D], natural column order, d ascending, every byte
+// <= 255 - P2.  sweep_geometry_cost lays the buffers out for them (gm is not used: the caller need not allocate it).  The caller records
+// ev[0] and queues the volume's producer on `st` first; ev[1..3] are recorded here, at the same places as sweep_run.
+void sweep_geometry_cost(int W, int H, int D, int P1, int P2, int lr, int subpixel, SwDev* s, SweepSizes* z, int max_batch);
+hipError_t sweep_run_cost(const SwDev& s, int n, const uint8_t* cost, int16_t* dDisp, hipStream_t st, SweepBuffers& b, hipEvent_t* ev, bool side_overlap,
+                          bool lr_kernel = true);
+
 }  // namespace jnav_sgm

@@ -12,6 +12,14 @@ class SgmParams(C.Structure):
                 ("lr_max_diff", C.c_int32), ("subpixel", C.c_int32)]
 
 
+class SgmCostParams(C.Structure):
+    """include/jn_sgm_cost.h: where the sweeps' matching cost comes from."""
+    _fields_ = [("cost_function", C.c_int32), ("block_radius", C.c_int32), ("cost_shift", C.c_int32), ("cost_max", C.c_int32)]
+
+
+SGM_COST_SAD3, SGM_COST_BLOCK_SSD, SGM_COST_EXTERNAL = 0, 1, 2
+
+
 class SgmTimes(C.Structure):
     _fields_ = [("prefilter", C.c_float), ("paths", C.c_float), ("wta", C.c_float), ("total", C.c_float)]
 
@@ -32,12 +40,20 @@ def _bind():
         L.jn_sgm_debug_ptr.restype = vp
         L.jn_sgm_submit_scan.argtypes = [vp, i32, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp]
         L.jn_sgm_wait.argtypes = [vp, i32]
+        L.jn_sgm_cost_params_default.argtypes = [C.POINTER(SgmCostParams)]
+        L.jn_sgm_cost_params_default.restype = None
+        L.jn_sgm_create_cost.argtypes = [C.POINTER(SgmParams), C.POINTER(SgmCostParams), i32, i32, i32, i32, C.POINTER(vp)]
+        L.jn_sgm_cost_volume.argtypes = [vp, i32, vp, vp, i32, i64, vp]
+        L.jn_sgm_aggregate_batch.argtypes = [vp, i32, vp, vp]
         L._sgm_bound = True
     return L
 
 
 SGM_EXPORTS = ["jn_sgm_params_default", "jn_sgm_create", "jn_sgm_destroy", "jn_sgm_process_batch", "jn_sgm_last_times",
                "jn_sgm_disparity_to_u8", "jn_sgm_debug_ptr", "jn_sgm_submit_scan", "jn_sgm_wait"]
+
+
+SGM_COST_EXPORTS = ["jn_sgm_cost_params_default", "jn_sgm_create_cost", "jn_sgm_cost_volume", "jn_sgm_aggregate_batch"]
 
 
 class Sgm:
@@ -51,12 +67,36 @@ class Sgm:
             setattr(p, k, v)
         return p
 
-    def __init__(self, param, width, height, max_batch=1, device=0):
+    @staticmethod
+    def cost_parameters(**overrides):
+        """jn_sgm_cost_params_default (the block-SSD cost, r = 2, cost_shift = 5, cost_max = 127) with overrides."""
+        c = SgmCostParams()
+        _bind().jn_sgm_cost_params_default(C.byref(c))
+        for k, v in overrides.items():
+            if not hasattr(c, k):
+                raise AttributeError(k)
+            setattr(c, k, v)
+        return c
+
+    def __init__(self, param, width, height, max_batch=1, device=0, cost=None):
+        """cost: an SgmCostParams (include/jn_sgm_cost.h) or None for jn_sgm.h's own 1x3 SAD."""
         self._L = _bind()
         self.param, self.width, self.height, self.max_batch, self.device = param, int(width), int(height), int(max_batch), int(device)
+        self.cost = cost
         h = C.c_void_p()
-        _lib.check(self._L.jn_sgm_create(C.byref(param), width, height, max_batch, device, C.byref(h)), "jn_sgm_create")
+        if cost is None:
+            _lib.check(self._L.jn_sgm_create(C.byref(param), width, height, max_batch, device, C.byref(h)), "jn_sgm_create")
+        else:
+            _lib.check(self._L.jn_sgm_create_cost(C.byref(param), C.byref(cost), width, height, max_batch, device, C.byref(h)), "jn_sgm_create_cost")
         self._h = h
+
+    def cost_volume(self, n, dI1, dI2, pitch, image_stride, dCost):
+        """Producer only (a BLOCK_SSD handle): dCost [n][H][W][D] u8, natural column order, d ascending (jn_sgm_cost_volume)."""
+        _lib.check(self._L.jn_sgm_cost_volume(self._h, n, dI1, dI2, pitch, image_stride, dCost), "jn_sgm_cost_volume")
+
+    def aggregate(self, n, dCost, dDisp):
+        """Consumer only: 8 paths + WTA + L/R + sub-pixel over a caller's volume (jn_sgm_aggregate_batch)."""
+        _lib.check(self._L.jn_sgm_aggregate_batch(self._h, n, dCost, dDisp), "jn_sgm_aggregate_batch")
 
     def process_batch(self, n, dI1, dI2, pitch, image_stride, dDisp):
         _lib.check(self._L.jn_sgm_process_batch(self._h, n, dI1, dI2, pitch, image_stride, dDisp), "jn_sgm_process_batch")

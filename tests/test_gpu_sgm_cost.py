@@ -1,0 +1,187 @@
+"""The SGM mode over a cost volume (include/jn_sgm_cost.h) on the GPU, bit for bit against its definition (tests/sgm_cost_def.py): the
+block-SSD producer (k_sgc_volume), the sweeps that read a volume (k_swc_h / k_swc_w) tied to the ones that compute their cost, the two
+together, the pipelined slots with the scan tail, and the SAD3 handle."""
+import numpy as np
+import pytest
+
+import matcher_cases as mc
+import sgm_cost_def as cd
+from matcher_run import run, LEFT_POISON, RIGHT_POISON
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev(jn):
+    from jackal_navigation_amd.device import DeviceArray
+    return DeviceArray
+
+
+def _pair(oracle, scene, W, H, seed):
+    if scene == "synth":
+        return oracle.synth_pair(W, H, 40, seed)
+    return mc.PAIRS[scene](W, H, seed)
+
+
+VOLUME_CASES = [
+    # W, H, D, r, shift, cost_max, P2, scene, n, extra, pad, gap
+    (200, 50, 64, 2, 5, 127, 60, "synth", 1, 0, 0, 0),
+    (133, 41, 128, 3, 5, 127, 60, "synth", 2, 0, 0, 0),          # a width that is no multiple of 32
+    (100, 37, 256, 4, 6, 100, 60, "synth", 1, 0, 0, 0),          # a frame narrower than D
+    (97, 40, 64, 2, 0, 195, 60, "noise", 1, 0, 0, 0),            # cost_shift = 0: cost_max saturates
+    (71, 35, 128, 4, 12, 127, 60, "noise", 1, 0, 0, 0),          # the largest shift
+    (32, 24, 64, 4, 3, 195, 60, "saw", 1, 0, 0, 0),              # every pair at the largest SSD a 9x9 block can have
+    (32, 24, 64, 4, 5, 195, 60, "peak", 1, 0, 0, 0),             # one candidate at cost 0 among the largest
+    (28, 19, 128, 2, 2, 150, 60, "peak", 1, 0, 0, 0),
+    (157, 43, 64, 3, 4, 90, 100, "synth", 2, 1, 5, 3),           # odd pitch, gap rows, n < max_batch
+]
+
+
+@pytest.mark.parametrize("W,H,D,r,shift,cmax,P2,scene,n,extra,pad,gap", VOLUME_CASES,
+                         ids=["%dx%d-D%d-r%d-s%d-m%d-%s" % (c[0], c[1], c[2], c[3], c[4], c[5], c[7]) for c in VOLUME_CASES])
+def test_cost_volume_equals_the_definition(jn, oracle, W, H, D, r, shift, cmax, P2, scene, n, extra, pad, gap):
+    DeviceArray = _dev(jn)
+    pairs = [_pair(oracle, scene, W, H, 70 + b) for b in range(n)]
+    pitch, rows = W + pad, H + gap
+    Lp = np.full((n, rows, pitch), LEFT_POISON, np.uint8); Rp = np.full((n, rows, pitch), RIGHT_POISON, np.uint8)
+    for b, (L, R) in enumerate(pairs):
+        Lp[b, :H, :W] = L; Rp[b, :H, :W] = R
+    dL, dR = DeviceArray.from_numpy(Lp), DeviceArray.from_numpy(Rp)
+    dC = DeviceArray.from_numpy(np.full((n, H, W, D), 0xEE, np.uint8))
+    p = jn.Sgm.parameters(num_disparities=D, P2=P2)
+    c = jn.Sgm.cost_parameters(block_radius=r, cost_shift=shift, cost_max=cmax)
+    with jn.Sgm(p, W, H, max_batch=n + extra, cost=c) as m:
+        m.cost_volume(n, dL.ptr, dR.ptr, pitch, rows * pitch, dC.ptr)
+    got = dC.numpy()
+    for b, (L, R) in enumerate(pairs):
+        want = cd.block_cost(L, R, D, p.prefilter_cap, r, shift, cmax)
+        assert np.array_equal(got[b], want), b
+    if shift == 0:
+        assert (got == cmax).mean() > 0.5
+    for a in (dL, dR, dC):
+        a.free()
+
+
+AGG_CASES = [
+    (150, 60, 64, dict()),
+    (190, 45, 128, dict(subpixel=1)),
+    (300, 40, 256, dict(subpixel=1, lr_max_diff=2)),
+    (141, 52, 64, dict(P1=7, P2=100, prefilter_cap=20)),          # 3 P2 > 255: the wide three-path volume
+    (333, 37, 128, dict(lr_max_diff=-1)),
+]
+
+
+@pytest.mark.parametrize("W,H,D,kw", AGG_CASES, ids=["%dx%d-D%d-%s" % (c[0], c[1], c[2], "+".join(sorted(c[3])) or "defaults") for c in AGG_CASES])
+def test_aggregating_the_sad3_volume_equals_the_plain_handle(jn, oracle, W, H, D, kw):
+    """The anchor that ties k_swc_* to k_sw_*: jn_sgm.h's own cost, built in numpy and brought as an EXTERNAL volume, must give the map
+    the plain handle computes from the images."""
+    DeviceArray = _dev(jn)
+    n = 2
+    pairs = [oracle.synth_pair(W, H, min(D - 16, 48), 500 + b) for b in range(n)]
+    p = jn.Sgm.parameters(num_disparities=D, **kw)
+    want, _, _ = run(jn, jn.Sgm, p, np.stack([a for a, _ in pairs]), np.stack([b for _, b in pairs]))
+    vol = np.stack([cd.sad3_volume(cd.prefilter(L, p.prefilter_cap), cd.prefilter(R, p.prefilter_cap), D) for L, R in pairs]).astype(np.uint8)
+    dC = DeviceArray.from_numpy(vol); dD = DeviceArray((n, H, W), np.int16)
+    with jn.Sgm(p, W, H, max_batch=n + 1, cost=jn.Sgm.cost_parameters(cost_function=cd.EXTERNAL)) as m:
+        m.aggregate(n, dC.ptr, dD.ptr)
+        got = dD.numpy().copy()
+        m.aggregate(1, dC.ptr + H * W * D, dD.ptr)               # the buffers are reused by a smaller batch
+        assert np.array_equal(dD.numpy()[0], want[1])
+        from jackal_navigation_amd import _lib
+        with pytest.raises(_lib.JnError):                       # image calls on an EXTERNAL handle are refused
+            m.process_batch(n, dC.ptr, dC.ptr, W, H * W, dD.ptr)
+        with pytest.raises(_lib.JnError):
+            m.cost_volume(n, dC.ptr, dC.ptr, W, H * W, dC.ptr)
+    assert np.array_equal(got, want)
+    assert (want >= 0).mean() > 0.3
+    dC.free(); dD.free()
+
+
+E2E_CASES = [
+    (170, 48, 64, 2, 5, 127, dict()),
+    (203, 41, 128, 3, 5, 127, dict(subpixel=1)),
+    (140, 36, 256, 4, 6, 120, dict(subpixel=1, lr_max_diff=2)),
+    (90, 44, 64, 2, 4, 150, dict(P1=9, P2=100)),                  # wide
+]
+
+
+@pytest.mark.parametrize("W,H,D,r,shift,cmax,kw", E2E_CASES, ids=["%dx%d-D%d-r%d-%s" % (c[0], c[1], c[2], c[3], "+".join(sorted(c[6])) or "defaults") for c in E2E_CASES])
+def test_block_ssd_handle_equals_the_definition_end_to_end(jn, oracle, W, H, D, r, shift, cmax, kw):
+    DeviceArray = _dev(jn)
+    n = 2
+    pairs = [oracle.synth_pair(W, H, min(D - 16, 40), 900 + b) for b in range(n)]
+    Ls, Rs = np.stack([a for a, _ in pairs]), np.stack([b for _, b in pairs])
+    p = jn.Sgm.parameters(num_disparities=D, **kw)
+    c = jn.Sgm.cost_parameters(block_radius=r, cost_shift=shift, cost_max=cmax)
+    dL, dR = DeviceArray.from_numpy(Ls), DeviceArray.from_numpy(Rs)
+    dD = DeviceArray((n, H, W), np.int16); dD2 = DeviceArray((n, H, W), np.int16); dC = DeviceArray((n, H, W, D), np.uint8)
+    with jn.Sgm(p, W, H, max_batch=n, cost=c) as m:
+        m.process_batch(n, dL.ptr, dR.ptr, W, H * W, dD.ptr)
+        t = m.last_times()
+        m.cost_volume(n, dL.ptr, dR.ptr, W, H * W, dC.ptr)
+        m.aggregate(n, dC.ptr, dD2.ptr)
+    got = dD.numpy()
+    assert np.array_equal(got, dD2.numpy())
+    for b in range(n):
+        want = cd.process(Ls[b], Rs[b], D, p.P1, p.P2, p.prefilter_cap, p.lr_max_diff, p.subpixel, r, shift, cmax)
+        assert np.array_equal(got[b], want), b
+    assert (got >= 0).mean() > 0.3
+    assert t["prefilter"] > 0 and t["total"] >= t["prefilter"]
+    for a in (dL, dR, dD, dD2, dC):
+        a.free()
+
+
+@pytest.mark.parametrize("sub,postfilter", [(0, False), (1, False), (1, True)])
+def test_pipelined_slots_with_the_scan_tail_equal_the_synchronous_route(jn, oracle, sub, postfilter):
+    """jn_sgm_submit_scan on three slots at once (slots 1 and 2 allocate their own cost volume): the int16 map, the mono8 map, bins and meta
+    must equal the synchronous call + jn_sgm_disparity_to_u8 + the stand-alone scan; one case with the post-filter attached."""
+    DeviceArray = _dev(jn)
+    from jackal_navigation_amd import node, postfilter as pf
+    W, H, D, n, S = 230, 90, 64, 2, 3
+    sp = node.scan_params(W, H)
+    lut = node.build_valid_disp_lut(sp, W, H)
+    frames = [[oracle.synth_pair(W, H, 40, 700 + 10 * k + t) for t in range(n)] for k in range(S)]
+    dL = [DeviceArray.from_numpy(np.stack([f[0] for f in fs])) for fs in frames]
+    dR = [DeviceArray.from_numpy(np.stack([f[1] for f in fs])) for fs in frames]
+    p = jn.Sgm.parameters(num_disparities=D, subpixel=sub)
+    fmt = pf.I16_SUB if sub else pf.I16
+    fp = pf.postfilter_params(fmt, speckle_size=40)
+    with jn.Sgm(p, W, H, max_batch=n, cost=jn.Sgm.cost_parameters()) as m:
+        want = []
+        for k in range(S):
+            dd = DeviceArray((n, H, W), np.int16); du = DeviceArray((n, H, W), np.uint8)
+            bins = DeviceArray((n, sp.bins), np.float64); meta = DeviceArray((n, 4), np.float64)
+            m.process_batch(n, dL[k].ptr, dR[k].ptr, W, H * W, dd.ptr)
+            if postfilter:
+                pf.disparity_postfilter(fp, n, dd.ptr, W, H)
+            m.to_u8(dd.ptr, du.ptr, n * H * W)
+            node.obstacle_scan(sp, n, du.ptr, lut.ptr, W, H, bins.ptr, meta.ptr)
+            want.append(tuple(a.numpy().copy() for a in (dd, du, bins, meta)))
+        outs = [tuple([DeviceArray((n, H, W), np.int16), DeviceArray((n, H, W), np.uint8), DeviceArray((n, sp.bins), np.float64),
+                       DeviceArray((n, 4), np.float64)]) for _ in range(S)]
+        for k in range(S):
+            if postfilter:
+                m.attach_postfilter(k, fp)
+            o = outs[k]
+            m.submit_scan(k, n, dL[k].ptr, dR[k].ptr, W, H * W, o[0].ptr, sp, lut.ptr, o[1].ptr, o[2].ptr, o[3].ptr)
+        for k in range(S):
+            m.wait(k)
+        got = [tuple(a.numpy().copy() for a in outs[k]) for k in range(S)]
+    for k in range(S):
+        for a, b in zip(want[k], got[k]):
+            assert np.array_equal(a, b), k
+        assert (want[k][0] >= 0).mean() > 0.3
+    b0 = cd.process(frames[0][0][0], frames[0][0][1], D, p.P1, p.P2, p.prefilter_cap, p.lr_max_diff, sub, 2, 5, 127)
+    if not postfilter:
+        assert np.array_equal(got[0][0][0], b0)
+
+
+def test_a_sad3_handle_from_create_cost_is_a_plain_handle(jn, oracle):
+    W, H, D = 210, 70, 128
+    L, R = oracle.synth_pair(W, H, 60, 42)
+    p = jn.Sgm.parameters(num_disparities=D, subpixel=1)
+    plain, _, _ = run(jn, jn.Sgm, p, L[None], R[None])
+    sad3 = lambda pp, w, h, max_batch=1: jn.Sgm(pp, w, h, max_batch=max_batch, cost=jn.Sgm.cost_parameters(cost_function=cd.SAD3, block_radius=0, cost_max=0))
+    got, _, _ = run(jn, sad3, p, L[None], R[None])
+    assert np.array_equal(got, plain)
+    from oracle.binding import SgmOracle
+    assert np.array_equal(plain[0], SgmOracle().process(SgmOracle.params(num_disparities=D, subpixel=1), L, R))
