@@ -29,6 +29,8 @@
 #include <cstdlib>
 #include <cstring>
 #include "../../include/jn_bm.h"
+#include "dev_owner.h"
+#include "hip_try.h"
 #include "kernels.h"          // launch_scan: the node's tail on the same stream (jn_bm_process_scan)
 #include "bm_mfma.h"
 #include "prefilter.h"          // JN_BM_COST_SSD: the matrix-core kernels
@@ -279,6 +281,7 @@ __global__ void __launch_bounds__(256) k_bm_finish_sub(BmDev s, int n, int band,
 // slots 1 .. kBmSlots-1 (jn_bm_submit_scan / jn_bm_wait) are allocated when first used.  Batches on different slots overlap on the GPU:
 // the memory-bound prefilter / finish / scan kernels of one run next to the issue-bound matching of another.
 struct BmSlot {
+  jnav::DevOwner own;          // what the slot made on the GPU
   uint8_t* g = nullptr;        // prefiltered rows [2 * max_batch][H][Wp]
   uint32_t* keys = nullptr;    // winners [2][max_batch][H][W]: cost << 8 | d
   unsigned long long* scan_scratch = nullptr;   // [max_batch][4], the scan tail's extrema
@@ -297,16 +300,8 @@ struct jn_bm {
   enum { kBmSlots = 6 };
   BmSlot slot[kBmSlots];
   jn_bm_times times = {};      // of the batch waited for last
+  __attribute__((visibility("hidden"))) ~jn_bm() = default;   // (not trivial with DevOwner in the slots; the library exports its C ABI only)
 };
-
-#define BM_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
 
 namespace {
 
@@ -350,15 +345,27 @@ hipError_t launch_bm_finish(hipStream_t st, const BmDev& s, int n, const uint8_t
 
 }  // namespace
 
+// What bm_ensure_slot makes; a failure returns half-way and leaves the release to it.
+static jn_status bm_slot_resources(jn_bm* h, BmSlot& x) {
+  if (h->q_bytes) HIP_TRY(x.own.alloc_bytes(reinterpret_cast<void**>(&x.q), h->q_bytes));
+  HIP_TRY(x.own.alloc(&x.g, h->g_bytes));
+  HIP_TRY(x.own.alloc(&x.keys, (size_t)2 * h->max_batch * h->H * h->W));
+  HIP_TRY(x.own.alloc(&x.scan_scratch, (size_t)4 * h->max_batch));
+  HIP_TRY(x.own.stream(&x.stream, hipStreamNonBlocking));
+  for (auto& e : x.ev) HIP_TRY(x.own.event(&e));
+  return JN_OK;
+}
+
+// A slot's buffers, stream and events, made once.  A slot that fails half-way gives back what it made and stays not ready.
 static jn_status bm_ensure_slot(jn_bm* h, int k) {
   BmSlot& x = h->slot[k];
   if (x.ready) return JN_OK;
-  if (h->q_bytes) BM_TRY(hipMalloc(reinterpret_cast<void**>(&x.q), h->q_bytes));
-  BM_TRY(hipMalloc(reinterpret_cast<void**>(&x.g), h->g_bytes));
-  BM_TRY(hipMalloc(reinterpret_cast<void**>(&x.keys), (size_t)2 * h->max_batch * h->H * h->W * sizeof(uint32_t)));
-  BM_TRY(hipMalloc(reinterpret_cast<void**>(&x.scan_scratch), sizeof(unsigned long long) * 4 * h->max_batch));
-  BM_TRY(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
-  for (auto& e : x.ev) BM_TRY(hipEventCreate(&e));
+  const jn_status e = bm_slot_resources(h, x);
+  if (e != JN_OK) {
+    x.own.release();
+    x = BmSlot();
+    return e;
+  }
   x.ready = true;
   return JN_OK;
 }
@@ -374,9 +381,7 @@ void jn_bm_destroy(jn_bm* h) {
   hipSetDevice(h->device);
   for (auto& x : h->slot) {
     if (x.stream) hipStreamSynchronize(x.stream);
-    hipFree(x.g); hipFree(x.keys); hipFree(x.scan_scratch); hipFree(x.q);
-    for (auto& e : x.ev) if (e) hipEventDestroy(e);
-    if (x.stream) hipStreamDestroy(x.stream);
+    x.own.release();
   }
   delete h;
 }
@@ -392,20 +397,18 @@ jn_status jn_bm_create(const jn_bm_params* p, int32_t W, int32_t H, int32_t max_
   if (ssd && (D & 31)) return JN_ERR_UNSUPPORTED;              // the matrix-core path covers the band with whole tiles of 32 candidates
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
-  BM_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   jn_bm* h = new jn_bm();
   h->p = *p; h->W = W; h->H = H; h->max_batch = max_batch; h->device = device;
   BmDev& s = h->dev;
   s.W = W; s.H = H; s.D = D; s.r = p->block_radius; s.cap = p->prefilter_cap; s.lr = p->lr_max_diff; s.subpixel = p->subpixel ? 1 : 0;
   s.padx = D + kBmPad; s.Wp = (W + 2 * s.padx + 3) & ~3;
-#define BM_CREATE_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { fprintf(stderr, "libjn_stereo: %s failed: %s\n", #expr, hipGetErrorString(e__)); jn_bm_destroy(h); return JN_ERR_NO_DEVICE; } } while (0)
   h->g_bytes = (size_t)2 * max_batch * H * s.Wp + 64;
   if (ssd) {
     jnav_bmq::Sizes z;
     jnav_bmq::geometry(W, H, D, p->block_radius, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->qdev, &z, max_batch);
     h->g_bytes = z.g; h->q_bytes = z.q;
   }
-#undef BM_CREATE_TRY
   const jn_status es = bm_ensure_slot(h, 0);
   if (es != JN_OK) { jn_bm_destroy(h); return es; }
   *out = h;
@@ -416,20 +419,20 @@ static jn_status bm_submit(jn_bm* h, int k, int32_t n, const uint8_t* dI1, const
                            const jn_scan_params* sp, const uint8_t* dLut, uint8_t* dU8, double* dBins, double* dMeta) {
   if (!h || k < 0 || k >= jn_bm::kBmSlots || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dDisp || pitch < h->W) return JN_ERR_INVALID;
   if (h->slot[k].pending) return JN_ERR_INVALID;               // one batch per slot: jn_bm_wait first
-  BM_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   const jn_status es = bm_ensure_slot(h, k);
   if (es != JN_OK) return es;
   BmSlot& x = h->slot[k];
   const BmDev& s = h->dev;
   hipStream_t st = x.stream;
-  BM_TRY(hipEventRecord(x.ev[0], st));
+  HIP_TRY(hipEventRecord(x.ev[0], st));
   uint32_t* keysL = x.keys;
   uint32_t* keysR = x.keys + (size_t)h->max_batch * s.H * s.W;
   if (h->p.cost_function == JN_BM_COST_SSD) {                  // squared differences: the banded int8 contraction on the matrix cores (bm_mfma.hip)
-    BM_TRY(jnav_bmq::run(h->qdev, n, dI1, dI2, pitch, (long long)image_stride, x.g, x.q, keysL, keysR, dDisp, dU8, st, x.ev));
+    HIP_TRY(jnav_bmq::run(h->qdev, n, dI1, dI2, pitch, (long long)image_stride, x.g, x.q, keysL, keysR, dDisp, dU8, st, x.ev));
   } else {
     hipLaunchKernelGGL(k_bm_prefilter, dim3((s.Wp / 4 + 255) / 256, s.H, 2 * n), dim3(256), 0, st, s, dI1, dI2, pitch, (long long)image_stride, n, x.g);
-    BM_TRY(hipEventRecord(x.ev[1], st));
+    HIP_TRY(hipEventRecord(x.ev[1], st));
     // Rows per band: whole turns of the kernel's ring (band + 2r = k (2r+1)) so that no staged row is wasted, as many as
     // fit 64 rows (halo overhead 2r / band), fewer turns while the launch would leave most of the 256 CUs idle (a lone pair).
     const int ring = 2 * s.r + 1;
@@ -437,14 +440,14 @@ static jn_status bm_submit(jn_bm* h, int k, int32_t n, const uint8_t* dI1, const
     while (turns > 2 && (long long)((s.W + 63) / 64) * ((s.H + turns * ring - 2 * s.r - 1) / (turns * ring - 2 * s.r)) * n < 1024) turns--;
     int band = turns * ring - 2 * s.r;
     if (const char* e = JN_HOOK_ENV("JN_BM_BAND")) band = std::min(std::max(atoi(e), 1), kBmMaxBand);
-    BM_TRY(launch_bm<0>(st, s, n, band, x.g, keysL));
-    if (s.lr >= 0) BM_TRY(launch_bm<1>(st, s, n, band, x.g, keysR));
-    BM_TRY(hipEventRecord(x.ev[2], st));
-    BM_TRY(launch_bm_finish(st, s, n, x.g, keysL, keysR, dDisp, dU8));
+    HIP_TRY(launch_bm<0>(st, s, n, band, x.g, keysL));
+    if (s.lr >= 0) HIP_TRY(launch_bm<1>(st, s, n, band, x.g, keysR));
+    HIP_TRY(hipEventRecord(x.ev[2], st));
+    HIP_TRY(launch_bm_finish(st, s, n, x.g, keysL, keysR, dDisp, dU8));
   }
   if (sp) jnav::launch_scan(st, *sp, n, nullptr, dU8, dLut, s.W, s.H, dBins, dMeta, x.scan_scratch);   // the node's tail, same stream
-  BM_TRY(hipEventRecord(x.ev[3], st));
-  BM_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(x.ev[3], st));
+  HIP_TRY(hipGetLastError());
   x.pending = true;
   return JN_OK;
 }
@@ -452,10 +455,10 @@ static jn_status bm_wait(jn_bm* h, int k) {
   if (!h || k < 0 || k >= jn_bm::kBmSlots) return JN_ERR_INVALID;
   BmSlot& x = h->slot[k];
   if (!x.pending) return JN_OK;
-  BM_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   x.pending = false;
-  BM_TRY(hipStreamSynchronize(x.stream));
-  BM_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(x.stream));
+  HIP_TRY(hipGetLastError());
   hipEventElapsedTime(&x.times.prefilter, x.ev[0], x.ev[1]);
   hipEventElapsedTime(&x.times.match, x.ev[1], x.ev[2]);
   hipEventElapsedTime(&x.times.finish, x.ev[2], x.ev[3]);

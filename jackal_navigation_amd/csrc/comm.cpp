@@ -8,6 +8,7 @@
 // RCCL is bound at run time: dlopen by soname returns the copy a host process already mapped (PyTorch ships its own
 // librccl.so.1), so a Python/torch host and this library talk to one RCCL; a plain C/C++ host gets /opt/rocm/lib's.
 #include "../../include/jn_stereo.h"
+#include "hip_try.h"
 #include "kernels.h"
 
 #include <dlfcn.h>
@@ -81,14 +82,6 @@ Rccl* rccl() {
       return JN_ERR_COMM;                                                                              \
     }                                                                                                  \
   } while (0)
-#define HIP_TRY_C(expr)                                                                                \
-  do {                                                                                                 \
-    hipError_t e__ = (expr);                                                                           \
-    if (e__ != hipSuccess) {                                                                           \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                                         \
-    }                                                                                                  \
-  } while (0)
 
 }  // namespace
 
@@ -127,7 +120,7 @@ jn_status jn_comm_create(const uint8_t id[JN_COMM_ID_BYTES], int32_t rank, int32
   if (!R) return JN_ERR_COMM;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
-  HIP_TRY_C(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   jn_comm* c = new jn_comm();
   c->rank = rank; c->world = world; c->device = device;
   ncclUniqueId u;
@@ -169,7 +162,7 @@ jn_status jn_comm_info(jn_comm* c, int32_t* rank, int32_t* world, int32_t* devic
 static jn_status grow_flat(jn_comm* c, size_t count) {
   if (count <= c->cap) return JN_OK;
   double* fresh = nullptr;
-  HIP_TRY_C(hipMalloc(reinterpret_cast<void**>(&fresh), count * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&fresh), count * sizeof(double)));
   if (c->flat) c->retired_dev.push_back(c->flat);
   c->flat = fresh; c->cap = count;
   return JN_OK;
@@ -181,21 +174,21 @@ static jn_status grow_flat(jn_comm* c, size_t count) {
 static jn_status queue_merge(jn_comm* c, Rccl* R, int n, int bins, double* dBins, double* dMeta, hipEvent_t ready, hipEvent_t done, double* packed = nullptr) {
   std::lock_guard<std::mutex> guard(c->m);
   if (c->dead.load()) return JN_ERR_COMM;
-  HIP_TRY_C(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->device));
   const size_t count = (size_t)n * (bins + 4);
   if (packed) {                                              // the caller's own packed buffer (k_scan_finish wrote it): reduce it in place, unpack
-    if (ready) HIP_TRY_C(hipStreamWaitEvent(c->stream, ready, 0));
+    if (ready) HIP_TRY(hipStreamWaitEvent(c->stream, ready, 0));
     RCCL_TRY(R, R->AllReduce(packed, packed, count, ncclDouble, ncclMin, c->comm, c->stream));
     launch_scan_pack(c->stream, n, bins, dBins, dMeta, packed, false);
-    if (done) HIP_TRY_C(hipEventRecord(done, c->stream));
+    if (done) HIP_TRY(hipEventRecord(done, c->stream));
     return JN_OK;
   }
   if (const jn_status gs = grow_flat(c, count); gs != JN_OK) return gs;
-  if (ready) HIP_TRY_C(hipStreamWaitEvent(c->stream, ready, 0));
+  if (ready) HIP_TRY(hipStreamWaitEvent(c->stream, ready, 0));
   launch_scan_pack(c->stream, n, bins, dBins, dMeta, c->flat, true);
   RCCL_TRY(R, R->AllReduce(c->flat, c->flat, count, ncclDouble, ncclMin, c->comm, c->stream));
   launch_scan_pack(c->stream, n, bins, dBins, dMeta, c->flat, false);
-  if (done) HIP_TRY_C(hipEventRecord(done, c->stream));
+  if (done) HIP_TRY(hipEventRecord(done, c->stream));
   return JN_OK;
 }
 
@@ -204,13 +197,13 @@ static jn_status queue_merge(jn_comm* c, Rccl* R, int n, int bins, double* dBins
 static jn_status bounded_stream_wait(jn_comm* c) {
   int timeout_ms = 30000;
   if (const char* e = getenv("JN_COMM_TIMEOUT_MS")) timeout_ms = atoi(e);
-  if (timeout_ms <= 0) { HIP_TRY_C(hipStreamSynchronize(c->stream)); }
+  if (timeout_ms <= 0) { HIP_TRY(hipStreamSynchronize(c->stream)); }
   else {
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
       const hipError_t q = hipStreamQuery(c->stream);
       if (q == hipSuccess) break;
-      if (q != hipErrorNotReady) { HIP_TRY_C(q); }
+      if (q != hipErrorNotReady) { HIP_TRY(q); }
       if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeout_ms)) { comm_abort(c); return JN_ERR_COMM; }
       std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
@@ -228,7 +221,7 @@ jn_status jn_scan_allreduce(jn_comm* c, int32_t n, int32_t bins, double* dBins, 
   if (st != JN_OK) return st;
   const jn_status ws = bounded_stream_wait(c);
   if (ws != JN_OK) return ws;
-  HIP_TRY_C(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 
@@ -245,7 +238,7 @@ jn_status jn_costmap_allreduce(jn_comm* c, const jn_scan_params* sp, const jn_co
   {
     std::lock_guard<std::mutex> guard(c->m);
     if (c->dead.load()) return JN_ERR_COMM;
-    HIP_TRY_C(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     if (const jn_status gs = grow_flat(c, count); gs != JN_OK) return gs;
     launch_costmap_pack(c->stream, (long long)count, dHits, c->flat, true);
     RCCL_TRY(R, R->AllReduce(c->flat, c->flat, count, ncclDouble, ncclMin, c->comm, c->stream));
@@ -254,7 +247,7 @@ jn_status jn_costmap_allreduce(jn_comm* c, const jn_scan_params* sp, const jn_co
   }
   const jn_status ws = bounded_stream_wait(c);
   if (ws != JN_OK) return ws;
-  HIP_TRY_C(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 
@@ -279,18 +272,18 @@ jn_status comm_merge_identity(jn_comm* c, int n, int bins) {
   {
     std::lock_guard<std::mutex> guard(c->m);
     if (c->dead.load()) return JN_ERR_COMM;
-    HIP_TRY_C(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     if (const jn_status gs = grow_flat(c, count); gs != JN_OK) return gs;
     if (count > c->inf_cap) {                                // the +inf source: pinned and persistent, so the fill below can be asynchronous
       double* fresh = nullptr;
-      HIP_TRY_C(hipHostMalloc(reinterpret_cast<void**>(&fresh), count * sizeof(double), hipHostMallocDefault));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fresh), count * sizeof(double), hipHostMallocDefault));
       for (size_t i = 0; i < count; i++) fresh[i] = INFINITY;
       if (c->h_inf) c->retired_host.push_back(c->h_inf);
       c->h_inf = fresh; c->inf_cap = count;
     }
     // ON the communicator's stream: ordered behind any in-place all-reduce on c->flat that is still running there (a null-stream copy
     // is not ordered against a non-blocking stream and could overwrite partially reduced chunks)
-    HIP_TRY_C(hipMemcpyAsync(c->flat, c->h_inf, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->flat, c->h_inf, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
     RCCL_TRY(R, R->AllReduce(c->flat, c->flat, count, ncclDouble, ncclMin, c->comm, c->stream));
   }
   // bounded like every other wait on the communicator (the peer this rank is feeding may itself be gone), and outside c->m so that an

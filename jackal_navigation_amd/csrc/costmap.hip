@@ -4,7 +4,7 @@
 // cells are integer results of individually rounded double arithmetic, so the bar for them is bit-exactness.
 //
 // The geometry (reprojection, ground model, cell of a point, bin of a bearing) and the wave-combined add are nav_tail.h's, shared with
-// subpix.hip.
+// scan.hip and subpix.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nav_tail.h"

@@ -795,19 +795,10 @@ jn_status jn_elas_create(const jn_elas_params* p, int32_t W, int32_t H, int32_t 
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
   HIP_TRY(hipSetDevice(device));
 
-  std::unique_ptr<jn_elas> h(new jn_elas());
   // any failure from here on releases whatever was allocated so far (jn_elas_destroy tolerates null buffers and
   // workers that were never started)
-#define CREATE_TRY(expr)                                                                      \
-  do {                                                                                        \
-    hipError_t e__ = (expr);                                                                  \
-    if (e__ != hipSuccess) {                                                                  \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      jn_elas_destroy(h.release());                                                           \
-      return JN_ERR_NO_DEVICE;                                                                \
-    }                                                                                         \
-  } while (0)
-  CREATE_TRY(configure_device_kernels());
+  std::unique_ptr<jn_elas, void (*)(jn_elas*)> h(new jn_elas(), jn_elas_destroy);
+  HIP_TRY(configure_device_kernels());
   h->p = *p; h->W = W; h->H = H; h->max_batch = max_batch; h->device = device;
   DevParams& dp = h->dp;
   memset(&dp, 0, sizeof(dp));
@@ -923,59 +914,58 @@ jn_status jn_elas_create(const jn_elas_params* p, int32_t W, int32_t H, int32_t 
     h->slots.emplace_back(new Slot());         // owned by the handle from the start: a failure below frees it too
     Slot* s = h->slots.back().get();
     DevOwner& own = s->own;
-    CREATE_TRY(own.stream(&s->stream, hipStreamNonBlocking));
+    HIP_TRY(own.stream(&s->stream, hipStreamNonBlocking));
     // Measured (profiles/r03_stage_a_priority_ab.txt): with stage A prioritised the pipelined 720p bench LOSES 12 % (17.5 k
     // against 20.2 k pairs/s) — the descriptor and support kernels of one slot then push the other slots' dense kernels
     // aside, and the GPU, not the host stage, is what the pipeline waits for.  Opt-in only: JN_STAGE_A_PRIORITY=1.
     if (getenv("JN_STAGE_A_PRIORITY") && atoi(getenv("JN_STAGE_A_PRIORITY")) != 0) {
       int least = 0, greatest = 0;
       if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
-        CREATE_TRY(own.stream(&s->stream_a, hipStreamNonBlocking, greatest));
+        HIP_TRY(own.stream(&s->stream_a, hipStreamNonBlocking, greatest));
     }
     // blocking-sync events: the slot worker sleeps while the GPU runs instead of spinning on a core that
     // the host stage (and, on a multi-GPU node, the other ranks) could use
-    for (int e = 0; e < EV_COUNT; e++) CREATE_TRY(own.event(&s->ev[e], hipEventBlockingSync));
-    CREATE_TRY(own.event(&s->ev_merged)); CREATE_TRY(own.event(&s->ev_head, hipEventDisableTiming)); CREATE_TRY(own.event(&s->ev_owner));
-    CREATE_TRY(own.alloc(&s->need_host, B)); CREATE_TRY(own.pinned(&s->h_need, B));
+    for (int e = 0; e < EV_COUNT; e++) HIP_TRY(own.event(&s->ev[e], hipEventBlockingSync));
+    HIP_TRY(own.event(&s->ev_merged)); HIP_TRY(own.event(&s->ev_head, hipEventDisableTiming)); HIP_TRY(own.event(&s->ev_owner));
+    HIP_TRY(own.alloc(&s->need_host, B)); HIP_TRY(own.pinned(&s->h_need, B));
     if (h->gate_stage_b) {                                   // no signal memory: the handle simply queues stage B after the host stage
       if (own.signal(&s->gate, 8) == hipSuccess) { s->gate[0] = 0; s->gate[1] = 0; }
       else (void)hipGetLastError();
     }
-    if (h->plane_flow) CREATE_TRY(own.alloc(&s->planes, plane_bytes(W, H, 2 * (int)B) + 64));
-    else CREATE_TRY(own.alloc(&s->desc, 2 * B * px));
-    CREATE_TRY(own.alloc(&s->d_can, B * dp.cw * dp.ch));
-    CREATE_TRY(own.alloc(&s->info, B)); CREATE_TRY(own.alloc(&s->payload, B * h->payload_cap));
+    if (h->plane_flow) HIP_TRY(own.alloc(&s->planes, plane_bytes(W, H, 2 * (int)B) + 64));
+    else HIP_TRY(own.alloc(&s->desc, 2 * B * px));
+    HIP_TRY(own.alloc(&s->d_can, B * dp.cw * dp.ch));
+    HIP_TRY(own.alloc(&s->info, B)); HIP_TRY(own.alloc(&s->payload, B * h->payload_cap));
     const size_t tiles = (size_t)((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH);
-    CREATE_TRY(own.alloc(&s->bin_count, 2 * B * tiles)); CREATE_TRY(own.alloc(&s->bin_list, 2 * B * tiles * kBinCap));
-    CREATE_TRY(own.alloc(&s->raw, 2 * B * px));
-    CREATE_TRY(own.alloc(&s->tmp, B * px)); CREATE_TRY(own.alloc(&s->label, B * px)); CREATE_TRY(own.alloc(&s->size, B * px));
-    CREATE_TRY(own.alloc(&s->scan_scratch, B * 4));
-    CREATE_TRY(own.alloc(&s->d_flat, B * (1024 + 4)));
+    HIP_TRY(own.alloc(&s->bin_count, 2 * B * tiles)); HIP_TRY(own.alloc(&s->bin_list, 2 * B * tiles * kBinCap));
+    HIP_TRY(own.alloc(&s->raw, 2 * B * px));
+    HIP_TRY(own.alloc(&s->tmp, B * px)); HIP_TRY(own.alloc(&s->label, B * px)); HIP_TRY(own.alloc(&s->size, B * px));
+    HIP_TRY(own.alloc(&s->scan_scratch, B * 4));
+    HIP_TRY(own.alloc(&s->d_flat, B * (1024 + 4)));
     const size_t grid_words = 2 * B * dp.gw * dp.gh * kGridWords;
-    CREATE_TRY(own.alloc(&s->mark, grid_words)); CREATE_TRY(own.alloc(&s->gridbits, grid_words));
-    CREATE_TRY(own.alloc(&s->recs, 2 * B * (size_t)h->tri_cap));
+    HIP_TRY(own.alloc(&s->mark, grid_words)); HIP_TRY(own.alloc(&s->gridbits, grid_words));
+    HIP_TRY(own.alloc(&s->recs, 2 * B * (size_t)h->tri_cap));
     s->scratch.resize(B);
     s->sides.resize(2 * B);
-    CREATE_TRY(own.pinned(&s->h_can, B * dp.cw * dp.ch)); CREATE_TRY(own.pinned(&s->h_info, B)); CREATE_TRY(own.pinned(&s->h_payload, B * h->payload_cap));
-    CREATE_TRY(own.pinned(&s->h_list, B * dp.cw * dp.ch * 3)); CREATE_TRY(own.pinned(&s->h_cnt, B));
-    CREATE_TRY(own.pinned(&s->h_arr, B * 2 * (size_t)h->arr_stride));
-    if (h->arr_stride > h->arr_cap) CREATE_TRY(own.alloc_bytes(&s->arr_scratch, arrange_scratch_bytes((int)B, h->arr_stride)));
-    CREATE_TRY(own.pinned(&s->h_arr_ok, B * 2));
+    HIP_TRY(own.pinned(&s->h_can, B * dp.cw * dp.ch)); HIP_TRY(own.pinned(&s->h_info, B)); HIP_TRY(own.pinned(&s->h_payload, B * h->payload_cap));
+    HIP_TRY(own.pinned(&s->h_list, B * dp.cw * dp.ch * 3)); HIP_TRY(own.pinned(&s->h_cnt, B));
+    HIP_TRY(own.pinned(&s->h_arr, B * 2 * (size_t)h->arr_stride));
+    if (h->arr_stride > h->arr_cap) HIP_TRY(own.alloc_bytes(&s->arr_scratch, arrange_scratch_bytes((int)B, h->arr_stride)));
+    HIP_TRY(own.pinned(&s->h_arr_ok, B * 2));
     if (h->gpu_delaunay) {
-      CREATE_TRY(own.alloc(&s->d_list, B * dp.cw * dp.ch * 3)); CREATE_TRY(own.alloc(&s->d_cnt, B));
-      CREATE_TRY(own.alloc(&s->d_arr, B * 2 * (size_t)h->arr_stride)); CREATE_TRY(own.alloc(&s->d_arr_ok, B * 2));
-      CREATE_TRY(hipMemset(s->payload, 0, B * h->payload_cap));
-      CREATE_TRY(hipStreamSynchronize(nullptr));             // hipMemset only queues the fill, and the slot's streams do not wait for the null stream: a late fill would wipe a payload
-      if (h->dt_gcap) CREATE_TRY(own.alloc(&s->dt_scratch, delaunay_gpu_scratch_bytes((int)B, h->dt_gcap)));      // (a side k_delaunay hands back leaves its part unwritten: never uninitialised memory)
+      HIP_TRY(own.alloc(&s->d_list, B * dp.cw * dp.ch * 3)); HIP_TRY(own.alloc(&s->d_cnt, B));
+      HIP_TRY(own.alloc(&s->d_arr, B * 2 * (size_t)h->arr_stride)); HIP_TRY(own.alloc(&s->d_arr_ok, B * 2));
+      HIP_TRY(hipMemset(s->payload, 0, B * h->payload_cap));
+      HIP_TRY(hipStreamSynchronize(nullptr));             // hipMemset only queues the fill, and the slot's streams do not wait for the null stream: a late fill would wipe a payload
+      if (h->dt_gcap) HIP_TRY(own.alloc(&s->dt_scratch, delaunay_gpu_scratch_bytes((int)B, h->dt_gcap)));      // (a side k_delaunay hands back leaves its part unwritten: never uninitialised memory)
     }
   }
   h->s_pitch = dp.pitch;
-  CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->s_img), 2 * (size_t)H * dp.pitch));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->s_D), 2 * px * sizeof(float)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->s_img), 2 * (size_t)H * dp.pitch));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->s_D), 2 * px * sizeof(float)));
   for (auto& s : h->slots) s->th = std::thread(slot_loop, h.get(), s.get());
   *out = h.release();
   return JN_OK;
-#undef CREATE_TRY
 }
 
 void jn_elas_destroy(jn_elas* h) {

@@ -12,6 +12,7 @@
 #include <new>
 #include <vector>
 #include "../../include/jn_stereo.h"
+#include "hip_try.h"
 #include "jpeg_host.h"
 
 namespace {
@@ -72,15 +73,6 @@ __global__ void __launch_bounds__(256) k_jpeg_idct_gray(const int16_t* __restric
 
 }  // namespace
 
-#define JPG_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
-
 // One eye: frame size against the caller's buffer, entropy decoding on the calling thread (the serial part), then upload +
 // inverse DCT.  `sc` is the calling thread's grow-only device scratch for this eye.
 // Coefficients travel host -> device from PINNED memory: from a pageable vector hipMemcpyAsync is staged and synchronous, and the pair
@@ -120,7 +112,7 @@ static jn_status jpeg_idct_launch(int32_t device, JpegScratch& sc, uint8_t* dOut
   const size_t need = sc.coef.size() * sizeof(int16_t);
   if (sc.dev != device || sc.cap < need) {                  // grow-only device buffer per calling thread, eye and device
     if (sc.p) { hipSetDevice(sc.dev); hipFree(sc.p); hipSetDevice(device); sc.p = nullptr; sc.cap = 0; }
-    JPG_TRY(hipMalloc(reinterpret_cast<void**>(&sc.p), need));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sc.p), need));
     sc.cap = need; sc.dev = device;
   }
   const size_t have = sc.coef.capacity() * sizeof(int16_t);
@@ -129,7 +121,7 @@ static jn_status jpeg_idct_launch(int32_t device, JpegScratch& sc, uint8_t* dOut
     if (hipHostRegister(sc.coef.data(), have, hipHostRegisterDefault) == hipSuccess) { sc.reg_ptr = sc.coef.data(); sc.reg_bytes = have; }
     else (void)hipGetLastError();                              // not fatal: the copy below is then staged by the runtime
   }
-  JPG_TRY(hipMemcpyAsync(sc.p, sc.coef.data(), need, hipMemcpyHostToDevice, nullptr));
+  HIP_TRY(hipMemcpyAsync(sc.p, sc.coef.data(), need, hipMemcpyHostToDevice, nullptr));
   QuantTable qt;
   memcpy(qt.q, sc.frame.quant, sizeof(qt.q));
   const int blocks = sc.frame.bw * sc.frame.bh;
@@ -147,10 +139,10 @@ jn_status jn_jpeg_decode_gray(int32_t device, const uint8_t* jpeg, int64_t nbyte
   if (st != JN_OK) return st;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
-  JPG_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   if ((st = jpeg_idct_launch(device, sc, dOut, out_pitch)) != JN_OK) return st;
-  JPG_TRY(hipStreamSynchronize(nullptr));
-  JPG_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 
@@ -205,12 +197,12 @@ jn_status jn_jpeg_decode_gray_pair(int32_t device, const uint8_t* jpegL, int64_t
   if (hp.w != *width || hp.h != *height) return JN_ERR_INVALID;                 // the two eyes must be the same size
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
-  JPG_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   jn_status st;
   if ((st = jpeg_idct_launch(device, scL, dOutL, out_pitch)) != JN_OK) return st;
   if ((st = jpeg_idct_launch(device, hp.sc, dOutR, out_pitch)) != JN_OK) return st;
-  JPG_TRY(hipStreamSynchronize(nullptr));
-  JPG_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
   return JN_OK;
 }
 

@@ -1,4 +1,4 @@
-// kernels.h — launchers of the gfx950 kernels (defined in kernels.hip).  Product code.
+// kernels.h — launchers of the gfx950 kernels (the ELAS path: kernels.hip; the node side: scan.hip; the tails: their own files).  Product code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +15,7 @@ hipError_t configure_device_kernels();
 
 // All launchers are asynchronous on `st`.  `n` = frames in the batch; per-frame arrays are laid out
 // frame-major with the strides given.
+inline dim3 grid2d(int W, int H, int z) { return dim3((W + 255) / 256, H, z); }   // one thread per pixel, 256 columns a workgroup
 
 // GPU stage A -------------------------------------------------------------------------------
 // Sobel + 16-byte descriptors (filter.cpp:372-416, descriptor.cpp:84-111), fused: desc [2n][H][W] uint4;
@@ -110,7 +111,7 @@ void launch_lr_sub(hipStream_t st, const DevParams& dp, int n, const FrameInfo* 
 void launch_adaptive_mean_sub(hipStream_t st, const DevParams& dph, int n, const FrameInfo* info, float* D, float* tmp);
 void launch_median(hipStream_t st, const DevParams& dp, int n, const FrameInfo* info, float* D, float* tmp);
 
-// Node side (point_cloud.cpp) -------------------------------------------------------------------
+// Node side (point_cloud.cpp; scan.hip) ---------------------------------------------------------
 void launch_to_u8(hipStream_t st, const float* D, uint8_t* out, int64_t count);
 void launch_valid_lut(hipStream_t st, const jn_scan_params& sp, int W, int H, uint8_t* lut);
 // scratch: [n][4] uint64.  If dD != nullptr the u8 map is produced from it first (fused), else dDisp is read.

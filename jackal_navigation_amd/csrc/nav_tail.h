@@ -1,30 +1,17 @@
-// nav_tail.h — what the navigation tails behind the matchers share (costmap.hip, subpix.hip, ground.hip; the slots of jn_api.cpp and
-// sgm.hip).  Product code.
+// nav_tail.h — what the scan and the navigation tails behind the matchers share (scan.hip, costmap.hip, subpix.hip, ground.hip,
+// localmap.hip, postfilter.hip; the slots of jn_api.cpp and sgm.hip).  Product code.
 //
-// Host side: the error macro, the calling thread's device scratch, and NavTails — the tails attached to one slot of a handle.
+// Host side: the calling thread's device scratch, and NavTails — the tails attached to one slot of a handle.
 // Device side (.hip files only): the reprojection and the ground model, cell and bin of a point, the order-preserving double <-> uint64
 // map, the wave-combined add, and the conversion of a map element to 1/16 pixel.  Every double operation is individually rounded on
 // purpose (include/jn_costmap.h, jn_subpix.h: the bar is bit-identity); do not contract or reassociate an expression here.
-// kernels.hip holds the same text under the names ScanDev / to_dev / reproject / is_ground / enc / dec: the evidence set's manifest pins
-// that file, and it switches to this header the next time the evidence set is re-published.  tests/test_gpu_costmap.py and
-// tests/test_gpu_subpix.py tie the two together on the GPU.
+// The scan itself (scan.hip) is built on the same definitions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
-#include <cstdio>
+#include "hip_try.h"
 #include "kernels.h"
-
-// Returns JN_ERR_NO_DEVICE from the calling function when a HIP call fails.  It prints its argument: keep the names of public constants
-// out of it (tests/test_abi.py counts the library's strings).
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess) {                                                                \
-      fprintf(stderr, "libjn_stereo: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return JN_ERR_NO_DEVICE;                                                              \
-    }                                                                                       \
-  } while (0)
 
 namespace jnav {
 
@@ -127,7 +114,7 @@ struct NavTails {
 // ---- device side -------------------------------------------------------------------------------------------------------------------
 #define DEV static __device__ __forceinline__
 
-struct NavGeom {                                                // kernels.hip's ScanDev, field for field
+struct NavGeom {                                                // jn_scan_params as the kernels take it (nav_geom)
   double Q[16], XR[9], XT[3];
   int ox, oy;
   double gp_h, gp_tan, gp_dist, fov, pi;

@@ -1,0 +1,301 @@
+// scan.hip — the node side (point_cloud.cpp) on gfx950: the mono8 conversion, the valid-disparity table, the obstacle scan, the rectification
+// front end and the point cloud.  Product code.
+//
+// What every matcher handle, the costmap, the ROS node and the stateless jn_* entry points call behind a disparity map; none of it is ELAS.
+// The reprojection, the ground model and the order-preserving double <-> uint64 map are nav_tail.h's, shared with the navigation tails,
+// whose bar is bit-identity with this scan.  Built like kernels.hip (-fhip-fp32-correctly-rounded-divide-sqrt: k_undistort_map / k_remap).
+#include "nav_tail.h"
+
+namespace jnav {
+
+// convertTo(CV_8U) (point_cloud.cpp:422) = round-half-even + saturate.
+DEV uint8_t f32_to_u8(float x) {
+  const float r = rintf(x);
+  return (uint8_t)(r < 0.f ? 0 : (r > 255.f ? 255 : (int)r));
+}
+__global__ void __launch_bounds__(256) k_to_u8(const float* __restrict__ D, uint8_t* __restrict__ out, long long count) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < count) out[i] = f32_to_u8(D[i]);
+}
+
+// cacheDisparityValues (point_cloud.cpp:104-147)
+__global__ void __launch_bounds__(256) k_valid_lut(NavGeom s, int W, int H, uint8_t* __restrict__ lut) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+  if (i >= W) return;
+  int d;
+  for (d = 3; d <= 255; d++) {
+    double X, Y, Z;
+    if (!nav_reproject(s, i, j, (double)d, X, Y, Z)) continue;
+    if (Z < 0.) continue;
+    if (nav_is_ground(s, X, Z)) continue;
+    break;
+  }
+  lut[((size_t)j * W + i) * 2] = (uint8_t)d;       // 256 wraps to 0 like the reference's uchar store (:142)
+  lut[((size_t)j * W + i) * 2 + 1] = 255;
+}
+
+// publishObstacleScan(Mat&) (point_cloud.cpp:213-296).  Per block: bins and the four extrema are
+// reduced in LDS (64-bit integer atomics on order-encoded doubles), then merged into global memory.
+// kFromCloud selects the -g flavour (publishPointCloud + publishObstacleScan(vector<Point3d>),
+// point_cloud.cpp:321-352, :149-211): every pixel with d >= 2 becomes a point, points on the ground
+// model are dropped, the rest are binned — instead of the LUT test of the default path.
+constexpr int kScanRows = 16;
+// kSgm: the disparities come from the SGM mode's winners (sgm_sweep.hip): the L/R check (k_sw_lr), the int16 map, its mono8 form
+// (jn_sgm_disparity_to_u8's rounding) and the scan in ONE pass — the three-kernel tail read the int16 map back twice and the mono8 map once.
+// The winners of a thread's 16 rows are requested together (a left winner, then the right image's winner it points at: two dependent
+// loads, which one row at a time would pay 16 times).
+template <bool kFromCloud, bool kSgm = false>
+__global__ void __launch_bounds__(256) k_scan(NavGeom s, const float* __restrict__ dD, uint8_t* __restrict__ dDisp,
+                                              const uint8_t* __restrict__ lut, int W, int H, unsigned long long* __restrict__ gbins,
+                                              unsigned long long* __restrict__ gmeta, SgmWinners sw = SgmWinners()) {
+  extern __shared__ unsigned long long lds[];      // [bins] + 4
+  unsigned long long* lbins = lds;
+  unsigned long long* lmeta = lds + s.bins;
+  const int frame = blockIdx.z;
+  for (int k = threadIdx.x; k < s.bins; k += 256) lbins[k] = ~0ull;
+  if (threadIdx.x < 4) lmeta[threadIdx.x] = (threadIdx.x & 1) ? 0ull : ~0ull;   // min slots start high, max slots low
+  __syncthreads();
+  // One thread walks kScanRows rows of one column.  The bearing of a pixel hardly depends on its row or
+  // disparity, so consecutive rows fall in the same bin: the running minimum stays in registers and reaches the
+  // LDS only when the bin changes (same-address LDS atomics from a whole wave would serialise otherwise).
+  const int i = blockIdx.x * 256 + threadIdx.x, j0 = blockIdx.y * kScanRows;
+  unsigned long long tmin = ~0ull, tmax = 0ull, rmin = ~0ull, rmax = 0ull;
+  int cur_bin = -1;
+  unsigned long long cur_min = ~0ull;
+  const int jend = min(j0 + kScanRows, H);
+  // Phase 1: the inputs of all of the thread's rows are requested TOGETHER (16 independent loads per array; round 4 fetched one row ahead
+  // and the kernel ran at one load latency per row), the mono8 map is written, and the rows whose disparity passes the LUT test (or d >= 2
+  // for the -g flavour) are noted in a mask.  Phase 2 visits only those rows, in ascending order — the order the running bin minimum expects.
+  uint32_t u8pk[kScanRows / 4] = {};                              // the mono8 values of this thread's rows
+  uint32_t cand = 0;
+  if (i < W) {
+    const size_t p0 = ((size_t)frame * H + j0) * W + i;
+    int dv[kScanRows];
+    if constexpr (kSgm) {
+      const int xk = W - 1 - i;                                   // the sweeps work on x-mirrored columns
+      uint32_t e[kScanRows], m[kScanRows];
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) e[r] = sw.dl[((size_t)frame * H + min(j0 + r, H - 1)) * W + xk];
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) m[r] = sw.minr[((size_t)frame * H + min(j0 + r, H - 1)) * W + min(xk + (int)(e[r] & 0xFFFFu), W - 1)];
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) {
+        const int d = (int)(e[r] & 0xFFFFu);
+        const bool ok = sw.lr < 0 || (xk + d < W && abs(d - (int)(m[r] & 0xFFFFu)) <= sw.lr);    // x - d >= 0 and the right image's winner there agrees
+        int v = ok ? (sw.subpixel ? (int)(int16_t)(e[r] >> 16) : d) : (sw.subpixel ? -16 : -1);
+        if (j0 + r < H) sw.disp[p0 + (size_t)r * W] = (int16_t)v;
+        if (v < 0) v = 0;
+        else if (sw.subpixel) { const int q = v >> 4, f = v & 15; v = q + ((f > 8 || (f == 8 && (q & 1))) ? 1 : 0); }   // half to even, as jn_sgm_disparity_to_u8
+        dv[r] = min(v, 255);
+        if (j0 + r < H) dDisp[p0 + (size_t)r * W] = (uint8_t)dv[r];
+      }
+    } else if (dD) {
+      float fd[kScanRows];
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) fd[r] = dD[((size_t)frame * H + min(j0 + r, H - 1)) * W + i];
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) { dv[r] = f32_to_u8(fd[r]); if (j0 + r < H) dDisp[p0 + (size_t)r * W] = (uint8_t)dv[r]; }
+    } else {
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) dv[r] = dDisp[((size_t)frame * H + min(j0 + r, H - 1)) * W + i];
+    }
+    uint32_t lt[kScanRows];
+    if (!kFromCloud) {
+#pragma unroll
+      for (int r = 0; r < kScanRows; r++) lt[r] = reinterpret_cast<const uint16_t*>(lut)[(size_t)min(j0 + r, H - 1) * W + i];       // :234
+    }
+#pragma unroll
+    for (int r = 0; r < kScanRows; r++) {
+      u8pk[r >> 2] |= (uint32_t)dv[r] << (8 * (r & 3));
+      const bool c = kFromCloud ? dv[r] >= 2 : (dv[r] >= (int)(lt[r] & 0xFF) && dv[r] <= (int)(lt[r] >> 8));
+      if (c && j0 + r < jend) cand |= 1u << r;
+    }
+  }
+  for (uint32_t mk = cand; mk; mk &= mk - 1) {
+    const int rr = __ffs((int)mk) - 1, j = j0 + rr;
+    const uint32_t w = rr < 8 ? (rr < 4 ? u8pk[0] : u8pk[1]) : (rr < 12 ? u8pk[2] : u8pk[3]);
+    const int d = (int)((w >> (8 * (rr & 3))) & 255u);
+    bool take;
+    double X = 0, Y = 0, Z = 0;
+    if (kFromCloud) take = nav_reproject(s, i, j, (double)d, X, Y, Z) && !nav_is_ground(s, X, Z);               // :324 (d >= 2: the mask), :166-172
+    else take = nav_reproject(s, i, j, (double)d, X, Y, Z);                                                  // (the LUT test: the mask)
+    if (take) {
+      const double th = atan2(Y, X);
+      const double deg = __dmul_rn(th, 180.) / s.pi;
+      const double r = sqrt(__dadd_rn(__dmul_rn(Y, Y), __dmul_rn(X, X)));
+      const unsigned long long et = nav_enc(th), er = nav_enc(r);
+      tmin = min(tmin, et); tmax = max(tmax, et); rmin = min(rmin, er); rmax = max(rmax, er);
+      const double kf = floor(__dmul_rn((double)s.bins, __dadd_rn(s.fov / 2., -deg)) / s.fov);   // :263
+      if (kf >= 0 && kf < (double)s.bins) {
+        const int k = (int)kf;
+        if (k != cur_bin) {
+          if (cur_bin >= 0) atomicMin(&lbins[cur_bin], cur_min);
+          cur_bin = k; cur_min = er;
+        } else cur_min = min(cur_min, er);
+      }
+    }
+  }
+  if (cur_bin >= 0) atomicMin(&lbins[cur_bin], cur_min);
+  // extrema: butterfly inside the wave, then one LDS atomic per wave — skipped by the (many) waves in which
+  // no pixel passed the test
+  if (__ballot(tmin != ~0ull) != 0ull) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    tmin = min(tmin, __shfl_xor(tmin, off)); tmax = max(tmax, __shfl_xor(tmax, off));
+    rmin = min(rmin, __shfl_xor(rmin, off)); rmax = max(rmax, __shfl_xor(rmax, off));
+  }
+  if ((threadIdx.x & 63) == 0) { atomicMin(&lmeta[0], tmin); atomicMax(&lmeta[1], tmax); atomicMin(&lmeta[2], rmin); atomicMax(&lmeta[3], rmax); }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < s.bins; k += 256)
+    if (lbins[k] != ~0ull) atomicMin(&gbins[(size_t)frame * s.bins + k], lbins[k]);
+  if (threadIdx.x < 4) {
+    const unsigned long long x = lmeta[threadIdx.x];
+    if (threadIdx.x & 1) { if (x != 0ull) atomicMax(&gmeta[frame * 4 + threadIdx.x], x); }
+    else { if (x != ~0ull) atomicMin(&gmeta[frame * 4 + threadIdx.x], x); }
+  }
+}
+__global__ void k_scan_init(int total_bins, int n, unsigned long long* gbins, unsigned long long* gmeta) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < total_bins) gbins[i] = ~0ull;
+  if (i < n * 4) gmeta[i] = (i & 1) ? 0ull : ~0ull;
+}
+__global__ void k_scan_finish(int total_bins, int n, unsigned long long* gbins, const unsigned long long* gmeta, double* meta, double* flat) {
+  // flat (may be null): the cross-rig merge's packed buffer [bins of all frames | extrema of all frames, maxima negated] — written here
+  // so that a batch with a communicator attached needs no separate pack launch (comm.cpp)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < total_bins) {
+    const unsigned long long k = gbins[i];
+    const double x = (k == ~0ull) ? 1e9 : nav_dec(k);                              // INF of point_cloud.cpp:54
+    reinterpret_cast<double*>(gbins)[i] = x;
+    if (flat) flat[i] = x;
+  }
+  if (i < n * 4) {
+    const unsigned long long k = gmeta[i];
+    const double init[4] = {400., -400., 1e9, -500.};                          // point_cloud.cpp:219-220
+    const bool untouched = (i & 1) ? (k == 0ull) : (k == ~0ull);
+    const double x = untouched ? init[i & 3] : nav_dec(k);
+    meta[i] = x;
+    if (flat) flat[total_bins + i] = (i & 1) ? -x : x;
+  }
+}
+
+// Cross-rig merge (comm.cpp): bins [n][bins] and extrema [n][4] of a batch <-> one packed buffer, the two maxima of
+// every frame negated (exact for doubles) so that the whole merge is a single MIN all-reduce.
+__global__ void k_scan_pack(int nb, int nm, double* __restrict__ bins, double* __restrict__ meta, double* __restrict__ flat, int pack) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nb) { if (pack) flat[i] = bins[i]; else bins[i] = flat[i]; }
+  else if (i < nb + nm) {
+    const int j = i - nb;
+    if (pack) { const double x = meta[j]; flat[i] = (j & 1) ? -x : x; }
+    else { const double x = flat[i]; meta[j] = (j & 1) ? -x : x; }
+  }
+}
+
+// initUndistortRectifyMap (point_cloud.cpp:553-554): for every rectified pixel the distorted source
+// position.  iR = inverse(P[:, :3] * R) comes from the host; the per-pixel math is OpenCV's, in
+// double, stored as float (the column walk is evaluated directly instead of by repeated addition).
+struct MapDev { double iR[9], k1, k2, p1, p2, k3, fx, fy, u0, v0; };
+__global__ void __launch_bounds__(256) k_undistort_map(MapDev m, int W, int H, float* __restrict__ mapx, float* __restrict__ mapy) {
+  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+  if (j >= W) return;
+  const double fj = (double)j, fi = (double)i;
+  const double _x = __dadd_rn(__dadd_rn(__dmul_rn(fj, m.iR[0]), __dmul_rn(fi, m.iR[1])), m.iR[2]);
+  const double _y = __dadd_rn(__dadd_rn(__dmul_rn(fj, m.iR[3]), __dmul_rn(fi, m.iR[4])), m.iR[5]);
+  const double _w = __dadd_rn(__dadd_rn(__dmul_rn(fj, m.iR[6]), __dmul_rn(fi, m.iR[7])), m.iR[8]);
+  const double w = __ddiv_rn(1.0, _w), x = __dmul_rn(_x, w), y = __dmul_rn(_y, w);
+  const double x2 = __dmul_rn(x, x), y2 = __dmul_rn(y, y), r2 = __dadd_rn(x2, y2), _2xy = __dmul_rn(__dmul_rn(2.0, x), y);
+  const double kr = __dadd_rn(1.0, __dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(m.k3, r2), m.k2), r2), m.k1), r2));
+  const double u = __dadd_rn(__dmul_rn(m.fx, __dadd_rn(__dadd_rn(__dmul_rn(x, kr), __dmul_rn(m.p1, _2xy)),
+                                                        __dmul_rn(m.p2, __dadd_rn(r2, __dmul_rn(2.0, x2))))), m.u0);
+  const double v = __dadd_rn(__dmul_rn(m.fy, __dadd_rn(__dadd_rn(__dmul_rn(y, kr), __dmul_rn(m.p1, __dadd_rn(r2, __dmul_rn(2.0, y2)))),
+                                                        __dmul_rn(m.p2, _2xy))), m.v0);
+  mapx[(size_t)i * W + j] = (float)u;
+  mapy[(size_t)i * W + j] = (float)v;
+}
+
+// remap, INTER_LINEAR, BORDER_CONSTANT 0 (point_cloud.cpp:440, :481)
+__global__ void __launch_bounds__(256) k_remap(const uint8_t* __restrict__ src, int sw, int sh, int spitch, long long sstride,
+                                               const float* __restrict__ mapx, const float* __restrict__ mapy,
+                                               uint8_t* __restrict__ dst, int W, int H, int dpitch, long long dstride) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, img = blockIdx.z;
+  if (x >= W) return;
+  const int sx = (int)rintf(__fmul_rn(mapx[(size_t)y * W + x], 32.0f)), sy = (int)rintf(__fmul_rn(mapy[(size_t)y * W + x], 32.0f));
+  const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
+  const uint8_t* S = src + (long long)img * sstride;
+  auto tap = [&](int xx, int yy) -> int { return (xx >= 0 && xx < sw && yy >= 0 && yy < sh) ? S[(size_t)yy * spitch + xx] : 0; };
+  const int p00 = tap(ix, iy), p01 = tap(ix + 1, iy), p10 = tap(ix, iy + 1), p11 = tap(ix + 1, iy + 1);
+  const int acc = (32 - fx) * (32 - fy) * p00 + fx * (32 - fy) * p01 + (32 - fx) * fy * p10 + fx * fy * p11;
+  dst[(long long)img * dstride + (size_t)y * dpitch + x] = (uint8_t)((acc + 512) >> 10);
+}
+
+// Point cloud (-g, point_cloud.cpp:321-352): column-major order (i outer, j inner) with d >= 2.
+__global__ void __launch_bounds__(256) k_pc_count(const uint8_t* __restrict__ disp, int W, int H, long long* __restrict__ col_count) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= W) return;
+  int c = 0;
+  for (int j = 0; j < H; j++) c += disp[(size_t)j * W + i] >= 2;
+  col_count[i + 1] = c;
+  if (i == 0) col_count[0] = 0;
+}
+__global__ void k_pc_scan(int W, long long* col_count) {   // tiny: one thread, W <= a few thousand
+  if (threadIdx.x == 0 && blockIdx.x == 0) for (int i = 1; i <= W; i++) col_count[i] += col_count[i - 1];
+}
+__global__ void __launch_bounds__(256) k_pc_scatter(NavGeom s, const uint8_t* __restrict__ disp, int W, int H,
+                                                    const long long* __restrict__ col_count, float* __restrict__ xyz) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= W) return;
+  long long o = col_count[i];
+  for (int j = 0; j < H; j++) {
+    const int d = disp[(size_t)j * W + i];
+    if (d < 2) continue;
+    double X, Y, Z;
+    if (!nav_reproject(s, i, j, (double)d, X, Y, Z)) { X = Y = Z = 0; }
+    xyz[3 * o] = (float)X; xyz[3 * o + 1] = (float)Y; xyz[3 * o + 2] = (float)Z; o++;
+  }
+}
+
+// ================================================================================================
+// launchers
+void launch_to_u8(hipStream_t st, const float* D, uint8_t* out, int64_t count) {
+  hipLaunchKernelGGL(k_to_u8, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, D, out, (long long)count);
+}
+void launch_valid_lut(hipStream_t st, const jn_scan_params& sp, int W, int H, uint8_t* lut) {
+  hipLaunchKernelGGL(k_valid_lut, grid2d(W, H, 1), dim3(256), 0, st, nav_geom(sp), W, H, lut);
+}
+void launch_scan(hipStream_t st, const jn_scan_params& sp, int n, const float* dD, uint8_t* dDisp, const uint8_t* lut,
+                 int W, int H, double* bins, double* meta, unsigned long long* scratch, double* flat, const SgmWinners* sgm) {
+  const NavGeom s = nav_geom(sp);
+  unsigned long long* gb = reinterpret_cast<unsigned long long*>(bins);
+  const int total = n * s.bins, m = total > n * 4 ? total : n * 4;
+  hipLaunchKernelGGL(k_scan_init, dim3((m + 255) / 256), dim3(256), 0, st, total, n, gb, scratch);
+  const dim3 sg((W + 255) / 256, (H + kScanRows - 1) / kScanRows, n);
+  if (sgm) hipLaunchKernelGGL((k_scan<false, true>), sg, dim3(256), (s.bins + 4) * sizeof(unsigned long long), st, s, nullptr, dDisp, lut, W, H, gb, scratch, *sgm);
+  else if (lut) hipLaunchKernelGGL((k_scan<false>), sg, dim3(256), (s.bins + 4) * sizeof(unsigned long long), st, s, dD, dDisp, lut, W, H, gb, scratch, SgmWinners());
+  else     hipLaunchKernelGGL((k_scan<true>), sg, dim3(256), (s.bins + 4) * sizeof(unsigned long long), st, s, dD, dDisp, lut, W, H, gb, scratch, SgmWinners());
+  hipLaunchKernelGGL(k_scan_finish, dim3((m + 255) / 256), dim3(256), 0, st, total, n, gb, scratch, meta, flat);
+}
+void launch_scan_pack(hipStream_t st, int n, int bins, double* dBins, double* dMeta, double* flat, bool pack) {
+  const int nb = n * bins, nm = n * 4;
+  hipLaunchKernelGGL(k_scan_pack, dim3((nb + nm + 255) / 256), dim3(256), 0, st, nb, nm, dBins, dMeta, flat, pack ? 1 : 0);
+}
+void launch_undistort_map(hipStream_t st, const double iR[9], const double K[9], const double D[5], int W, int H, float* mapx, float* mapy) {
+  MapDev m;
+  for (int i = 0; i < 9; i++) m.iR[i] = iR[i];
+  m.k1 = D[0]; m.k2 = D[1]; m.p1 = D[2]; m.p2 = D[3]; m.k3 = D[4];
+  m.fx = K[0]; m.fy = K[4]; m.u0 = K[2]; m.v0 = K[5];
+  hipLaunchKernelGGL(k_undistort_map, grid2d(W, H, 1), dim3(256), 0, st, m, W, H, mapx, mapy);
+}
+void launch_remap(hipStream_t st, int n, const uint8_t* src, int sw, int sh, int spitch, int64_t sstride, const float* mapx,
+                  const float* mapy, uint8_t* dst, int W, int H, int dpitch, int64_t dstride) {
+  hipLaunchKernelGGL(k_remap, grid2d(W, H, n), dim3(256), 0, st, src, sw, sh, spitch, (long long)sstride, mapx, mapy, dst, W, H, dpitch,
+                     (long long)dstride);
+}
+void launch_point_cloud(hipStream_t st, const jn_scan_params& sp, const uint8_t* disp, int W, int H, float* xyz, long long* col_count) {
+  const NavGeom s = nav_geom(sp);
+  hipLaunchKernelGGL(k_pc_count, dim3((W + 255) / 256), dim3(256), 0, st, disp, W, H, col_count);
+  hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(64), 0, st, W, col_count);
+  hipLaunchKernelGGL(k_pc_scatter, dim3((W + 255) / 256), dim3(256), 0, st, s, disp, W, H, col_count, xyz);
+}
+
+}  // namespace jnav

@@ -3,8 +3,8 @@
 //
 // No reference counterpart; the definition is in jn_subpix.h, its scalar restatement (the checker) in tests/subpix_def.py.  The anchor
 // of that header — bit-identity with jn_obstacle_scan_cloud, jn_obstacle_costmap(from_cloud = 1) and jn_point_cloud on integer maps —
-// holds because the reprojection, the ground model, the cell and the bin of a point are nav_tail.h's own functions, the ones costmap.hip
-// calls (kernels.hip's k_scan<true> holds the same text, see nav_tail.h), and the grid classification is costmap.hip's own finish kernel.
+// holds because the reprojection, the ground model, the cell and the bin of a point are nav_tail.h's own functions, the ones scan.hip and
+// costmap.hip call, and the grid classification is costmap.hip's own finish kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>

@@ -1,4 +1,5 @@
-"""Create / use / destroy handles (ELAS, then SGM with all its slots) repeatedly and from several threads; device memory must come back."""
+"""Create / use / destroy handles (ELAS, then SGM and block matching with all their slots) repeatedly and from several threads; device memory
+must come back."""
 import os, sys, threading
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,4 +57,20 @@ for it in range(25):
 print("SGM, 8 slots: free MB after 3 cycles %.0f, after 25 cycles %.0f" % (base, free_mb()))
 assert abs(free_mb() - base) < 64, "device memory leak (SGM)"
 assert all(np.array_equal(d.numpy(), ref_sgm) for d in dd), "SGM slots disagree"
+# And the block-matching handle, the sum of absolute differences and the matrix cores' squared differences: its six slots.
+S = 6
+for cost, name in ((0, "SAD"), (1, "SSD")):
+    base = None
+    for it in range(25):
+        with jn.Bm(jn.Bm.parameters(num_disparities=64, cost_function=cost), W, H, max_batch=1) as m:
+            for s in range(S):
+                m.submit_scan(s, 1, dL.ptr, dR.ptr, W, H * W, dd[s].ptr, sp, lut.ptr, u8[s].ptr, bins[s].ptr, meta[s].ptr)
+            for s in range(S):
+                m.wait(s)
+        if it == 2:
+            base = free_mb()
+            ref_bm = dd[0].numpy().copy()
+    print("BM %s, 6 slots: free MB after 3 cycles %.0f, after 25 cycles %.0f" % (name, base, free_mb()))
+    assert abs(free_mb() - base) < 64, "device memory leak (BM %s)" % name
+    assert all(np.array_equal(d.numpy(), ref_bm) for d in dd[:S]), "BM slots disagree"
 print("lifecycle OK")

@@ -3,8 +3,8 @@
   python3 scripts/make_pmc_json.py <tag> <out.json>     (reads gpurun_out/<tag>_pmc_{FETCH,WRITE}_SIZE.txt, <tag>_sq{1,2}.txt,
                                                           <tag>_slots1_summary.txt)
 FETCH_SIZE is doubled (gfx950 tallies 128-byte requests at 64 B for 16-byte-per-lane streaming loads, MI355X_MICROARCH.md,
-HBM section); WRITE_SIZE is taken as is.  The file records the sha256 of kernels.hip it was measured with: bench.py
-reports `traffic` only when that still matches."""
+HBM section); WRITE_SIZE is taken as is.  The file records the sha256 of kernels.hip (the ELAS path) and scan.hip (the scan behind it) it was
+measured with: bench.py reports `traffic` only when the former still matches."""
 import hashlib, json, os, re, subprocess, sys
 tag, out = sys.argv[1], sys.argv[2]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +43,7 @@ doc = {
     "correction": "gfx950: FETCH_SIZE x 2 (MI355X_MICROARCH.md, HBM section) — settled by a probe for the loads these kernels issue: a buffer streamed once with raw_buffer_load of 4, 8 and 16 bytes per lane "
                   "shows HALF the bytes read in FETCH_SIZE in all three cases (scripts/probes/fetch_size_probe.hip, profiles/%s_fetch_size_probe.txt); WRITE_SIZE as is; KB = 1024 B" % tag,
     "kernels_hip_sha256": hashlib.sha256(open(os.path.join(root, "jackal_navigation_amd", "csrc", "kernels.hip"), "rb").read()).hexdigest(),
+    "scan_hip_sha256": hashlib.sha256(open(os.path.join(root, "jackal_navigation_amd", "csrc", "scan.hip"), "rb").read()).hexdigest(),
     "commit": subprocess.run(["git", "-C", root, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip(),
 }
 for name in sorted(set(fetch) | set(write)):

@@ -161,7 +161,7 @@ def test_elas_scenes_equal_the_definition(jn, W, H, kind):
 
 
 def test_the_binned_points_are_the_point_clouds(jn):
-    """costmap.hip restates kernels.hip's reprojection.  With the -g rule, the ground test switched off and min_hits = 1 the occupied cells
+    """costmap.hip and jn_point_cloud (scan.hip) reproject through the same nav_tail.h functions.  With the -g rule, the ground test switched off and min_hits = 1 the occupied cells
     must be the cells of jn_point_cloud's points (float32, so a point within float32 rounding of a cell edge may sit on either side)."""
     from jackal_navigation_amd import costmap, node
     from jackal_navigation_amd.device import DeviceArray
