@@ -18,6 +18,7 @@
 #include "../../include/jn_postfilter.h"
 #include "sgm_sweep.h"
 #include "bm_mfma.h"            // the block-SSD cost volume (jn_sgm_cost.h): the matrix-core pass with bytes in place of a winner
+#include "census.h"             // the census / Hamming cost volume (jn_sgm_cost.h)
 #include "dev_owner.h"
 #include "nav_tail.h"           // kernels.h's launch_scan, and NavTails: the node's tails on a slot's stream (jn_sgm_submit_scan)
 
@@ -40,10 +41,14 @@ struct jn_sgm {
   jnav_sgm::SwDev sw = {};
   jnav_sgm::SweepSizes sizes = {};
   // include/jn_sgm_cost.h: where the costs of the sweeps come from.  SAD3 (jn_sgm_create): computed inside them; BLOCK_SSD: a slot's own
-  // volume, written by bm_mfma.hip's producer ahead of the sweeps; EXTERNAL: the caller's volume (jn_sgm_aggregate_batch)
+  // volume, written by bm_mfma.hip's producer ahead of the sweeps; CENSUS: the same with census.hip's producer; EXTERNAL: the caller's
+  // volume (jn_sgm_aggregate_batch)
   jn_sgm_cost_params cost = {JN_SGM_COST_SAD3, 0, 0, 0};
   jnav_bmq::QDev bq = {};
   jnav_bmq::Sizes bqz = {};
+  jnav_census::CDev cq = {};
+  jnav_census::Sizes cqz = {};
+  bool makes_volume() const { return cost.cost_function == JN_SGM_COST_BLOCK_SSD || cost.cost_function == JN_SGM_COST_CENSUS; }
   // One slot: its own sweep buffers, stream and events.  Slot 0 is made with the handle (jn_sgm_process_batch runs on it), the others the
   // first time they are used (jn_sgm_submit_scan / jn_sgm_wait).  Batches on different slots overlap on the GPU: the upward sweep's tail
   // (the last blocks of its parallelogram run alone) is filled by the next batch's horizontal and downward sweeps.
@@ -51,9 +56,10 @@ struct jn_sgm {
   struct Slot {
     jnav::DevOwner own;
     jnav_sgm::SweepBuffers sb = {};
-    uint8_t* cost = nullptr;                    // BLOCK_SSD: the slot's cost volume [max_batch][H][W][D] ...
-    uint8_t* bg = nullptr;                      // ... and the producer's prefiltered rows and patch norms (bm_mfma.h)
+    uint8_t* cost = nullptr;                    // BLOCK_SSD, CENSUS: the slot's cost volume [max_batch][H][W][D] ...
+    uint8_t* bg = nullptr;                      // ... BLOCK_SSD: the producer's prefiltered rows and patch norms (bm_mfma.h)
     int32_t* bQ = nullptr;
+    void* csig = nullptr;                       // ... CENSUS: the signatures of both eyes (census.h)
     hipStream_t stream = nullptr;               // its own, or with JN_SGM_STREAMS a lower slot's (`shared`: not in `own`)
     hipEvent_t ev[4] = {};
     hipEvent_t ev_end = nullptr;                // recorded behind EVERYTHING a submit queued (sweeps + the scan tail); what jn_sgm_wait waits for
@@ -74,11 +80,12 @@ static jn_status sgm_slot_resources(jn_sgm* h, int slot) {
   jn_sgm::Slot& s = h->slots[slot];
   const jnav_sgm::SweepSizes& z = h->sizes;
   if (h->cost.cost_function == JN_SGM_COST_SAD3) HIP_TRY(s.own.alloc(&s.sb.gm, z.gm));
+  if (h->makes_volume()) HIP_TRY(s.own.alloc(&s.cost, (size_t)h->max_batch * h->W * h->H * h->sw.D));
   if (h->cost.cost_function == JN_SGM_COST_BLOCK_SSD) {
-    HIP_TRY(s.own.alloc(&s.cost, (size_t)h->max_batch * h->W * h->H * h->sw.D));
     HIP_TRY(s.own.alloc(&s.bg, h->bqz.g));
     HIP_TRY(s.own.alloc_bytes(reinterpret_cast<void**>(&s.bQ), h->bqz.q));
   }
+  if (h->cost.cost_function == JN_SGM_COST_CENSUS) HIP_TRY(s.own.alloc_bytes(&s.csig, h->cqz.sig));
   HIP_TRY(s.own.alloc(&s.sb.volF, z.vol * (h->sw.wide ? 2 : 1)));
   HIP_TRY(s.own.alloc(&s.sb.volH0, z.vol));
   HIP_TRY(s.own.alloc(&s.sb.volH1, z.vol));
@@ -112,7 +119,7 @@ static jn_status sgm_make_slot(jn_sgm* h, int slot) {
   if (e != JN_OK) {
     s.own.release();
     s.sb = {}; s.stream = nullptr; s.shared = false;
-    s.cost = nullptr; s.bg = nullptr; s.bQ = nullptr;
+    s.cost = nullptr; s.bg = nullptr; s.bQ = nullptr; s.csig = nullptr;
     for (auto& v : s.ev) v = nullptr;
     return e;
   }
@@ -129,14 +136,20 @@ static void sgm_read_times(jn_sgm* h, const jn_sgm::Slot& s) {
   hipEventElapsedTime(&t.total, s.ev[0], s.ev[3]);
 }
 
-// The whole mode of a slot's batch on its stream: the sweeps, behind the cost volume's producer on a BLOCK_SSD handle (ev[0] .. ev[1] then
-// span the producer: jn_sgm_times.prefilter).
+// The cost volume of a BLOCK_SSD or CENSUS handle, queued on the slot's stream.
+static hipError_t sgm_queue_volume(jn_sgm* h, jn_sgm::Slot& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, uint8_t* cost) {
+  if (h->cost.cost_function == JN_SGM_COST_CENSUS) return jnav_census::cost_volume(h->cq, n, dI1, dI2, pitch, stride, s.csig, h->cost.cost_max, cost, s.stream);
+  return jnav_bmq::cost_volume(h->bq, n, dI1, dI2, pitch, stride, s.bg, s.bQ, h->cost.cost_shift, h->cost.cost_max, cost, s.stream);
+}
+
+// The whole mode of a slot's batch on its stream: the sweeps, behind the cost volume's producer on a BLOCK_SSD or CENSUS handle (ev[0] ..
+// ev[1] then span the producer: jn_sgm_times.prefilter).
 static hipError_t sgm_queue(jn_sgm* h, jn_sgm::Slot& s, int n, const uint8_t* dI1, const uint8_t* dI2, int pitch, long long stride, int16_t* dDisp,
                             bool side_overlap, bool lr_kernel) {
   if (h->cost.cost_function == JN_SGM_COST_SAD3) return jnav_sgm::sweep_run(h->sw, n, dI1, dI2, pitch, stride, dDisp, s.stream, s.sb, s.ev, side_overlap, lr_kernel);
   hipError_t e;
   if ((e = hipEventRecord(s.ev[0], s.stream)) != hipSuccess) return e;
-  if ((e = jnav_bmq::cost_volume(h->bq, n, dI1, dI2, pitch, stride, s.bg, s.bQ, h->cost.cost_shift, h->cost.cost_max, s.cost, s.stream)) != hipSuccess) return e;
+  if ((e = sgm_queue_volume(h, s, n, dI1, dI2, pitch, stride, s.cost)) != hipSuccess) return e;
   return jnav_sgm::sweep_run_cost(h->sw, n, s.cost, dDisp, s.stream, s.sb, s.ev, side_overlap, lr_kernel);
 }
 
@@ -185,11 +198,13 @@ jn_status jn_sgm_create_cost(const jn_sgm_params* p, const jn_sgm_cost_params* c
   if (!p || !c || !out || W < 8 || H < 8 || W > 8192 || H > 8192 || max_batch < 1) return JN_ERR_INVALID;
   *out = nullptr;
   if (c->cost_function == JN_SGM_COST_SAD3) return jn_sgm_create(p, W, H, max_batch, device, out);
-  if (c->cost_function != JN_SGM_COST_BLOCK_SSD && c->cost_function != JN_SGM_COST_EXTERNAL) return JN_ERR_UNSUPPORTED;
+  if (c->cost_function != JN_SGM_COST_BLOCK_SSD && c->cost_function != JN_SGM_COST_EXTERNAL && c->cost_function != JN_SGM_COST_CENSUS) return JN_ERR_UNSUPPORTED;
   const int D = p->num_disparities;
   if ((D != 64 && D != 128 && D != 256) || p->prefilter_cap < 1 || p->prefilter_cap > 31 || p->P1 < 0 || p->P2 < p->P1 || p->P2 > 254) return JN_ERR_UNSUPPORTED;
   if (c->cost_function == JN_SGM_COST_BLOCK_SSD &&
       (c->block_radius < 2 || c->block_radius > 4 || c->cost_shift < 0 || c->cost_shift > 12 || c->cost_max < 1 || c->cost_max + p->P2 > 255))
+    return JN_ERR_UNSUPPORTED;
+  if (c->cost_function == JN_SGM_COST_CENSUS && (c->block_radius < 2 || c->block_radius > 4 || c->cost_max < 1 || c->cost_max + p->P2 > 255))   // (cost_shift: not used)
     return JN_ERR_UNSUPPORTED;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
@@ -199,6 +214,7 @@ jn_status jn_sgm_create_cost(const jn_sgm_params* p, const jn_sgm_cost_params* c
   jnav_sgm::sweep_geometry_cost(W, H, D, p->P1, p->P2, p->lr_max_diff, p->subpixel, &h->sw, &h->sizes, max_batch);
   h->sw.cap = p->prefilter_cap;
   if (c->cost_function == JN_SGM_COST_BLOCK_SSD) jnav_bmq::geometry(W, H, D, c->block_radius, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->bq, &h->bqz, max_batch);
+  if (c->cost_function == JN_SGM_COST_CENSUS) jnav_census::geometry(W, H, D, c->block_radius, &h->cq, &h->cqz, max_batch);
   const jn_status e = sgm_make_slot(h, 0);
   if (e != JN_OK) { jn_sgm_destroy(h); return e; }
   *out = h;
@@ -207,11 +223,11 @@ jn_status jn_sgm_create_cost(const jn_sgm_params* p, const jn_sgm_cost_params* c
 
 jn_status jn_sgm_cost_volume(jn_sgm* h, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride, uint8_t* dCost) {
   if (!h || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dCost || ((uintptr_t)dCost & 15) || pitch < h->W) return JN_ERR_INVALID;
-  if (h->cost.cost_function != JN_SGM_COST_BLOCK_SSD) return JN_ERR_UNSUPPORTED;
+  if (!h->makes_volume()) return JN_ERR_UNSUPPORTED;
   jn_sgm::Slot& s = h->slots[0];
   if (s.pending) return JN_ERR_INVALID;                         // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(jnav_bmq::cost_volume(h->bq, n, dI1, dI2, pitch, (long long)image_stride, s.bg, s.bQ, h->cost.cost_shift, h->cost.cost_max, dCost, s.stream));
+  HIP_TRY(sgm_queue_volume(h, s, n, dI1, dI2, pitch, (long long)image_stride, dCost));
   HIP_TRY(hipStreamSynchronize(s.stream));
   HIP_TRY(hipGetLastError());
   return JN_OK;

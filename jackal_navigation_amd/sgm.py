@@ -18,6 +18,7 @@ class SgmCostParams(C.Structure):
 
 
 SGM_COST_SAD3, SGM_COST_BLOCK_SSD, SGM_COST_EXTERNAL = 0, 1, 2
+SGM_COST_CENSUS = 4            # census / Hamming over a 5x5, 7x7 or 9x7 window (block_radius 2, 3, 4); 3 is no cost function
 
 
 class SgmTimes(C.Structure):
@@ -79,7 +80,8 @@ class Sgm:
         return c
 
     def __init__(self, param, width, height, max_batch=1, device=0, cost=None):
-        """cost: an SgmCostParams (include/jn_sgm_cost.h) or None for jn_sgm.h's own 1x3 SAD."""
+        """cost: an SgmCostParams (include/jn_sgm_cost.h) or None for jn_sgm.h's own 1x3 SAD; the census cost over a 9x7 window is
+        Sgm.cost_parameters(cost_function=sgm.SGM_COST_CENSUS, block_radius=4)."""
         self._L = _bind()
         self.param, self.width, self.height, self.max_batch, self.device = param, int(width), int(height), int(max_batch), int(device)
         self.cost = cost
@@ -91,7 +93,7 @@ class Sgm:
         self._h = h
 
     def cost_volume(self, n, dI1, dI2, pitch, image_stride, dCost):
-        """Producer only (a BLOCK_SSD handle): dCost [n][H][W][D] u8, natural column order, d ascending (jn_sgm_cost_volume)."""
+        """Producer only (a BLOCK_SSD or CENSUS handle): dCost [n][H][W][D] u8, natural column order, d ascending (jn_sgm_cost_volume)."""
         _lib.check(self._L.jn_sgm_cost_volume(self._h, n, dI1, dI2, pitch, image_stride, dCost), "jn_sgm_cost_volume")
 
     def aggregate(self, n, dCost, dDisp):
