@@ -16,6 +16,8 @@ from . import subpix  # noqa: F401
 from .subpix import SubpixParams, SUBPIX_EXPORTS, subpix_scan, subpix_costmap, subpix_point_cloud  # noqa: F401
 from . import localmap  # noqa: F401
 from .localmap import LocalMap, LocalMapParams, Pose2D, LOCALMAP_EXPORTS, localmap_params  # noqa: F401
+from . import plan  # noqa: F401
+from .plan import Plan, PlanParams, PlanRecord, PlanCmd, PLAN_EXPORTS, plan_params  # noqa: F401
 from . import postfilter  # noqa: F401
 from .postfilter import PostfilterParams, POSTFILTER_EXPORTS, postfilter_params, disparity_postfilter  # noqa: F401
 from . import ground, calib  # noqa: F401
