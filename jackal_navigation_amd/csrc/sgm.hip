@@ -153,6 +153,19 @@ static hipError_t sgm_queue(jn_sgm* h, jn_sgm::Slot& s, int n, const uint8_t* dI
   return jnav_sgm::sweep_run_cost(h->sw, n, s.cost, dDisp, s.stream, s.sb, s.ev, side_overlap, lr_kernel);
 }
 
+// The frame of the synchronous calls: slot 0 idle, `queue` on its stream, wait, the stage times where the call spans the sweeps.
+template <class Queue>
+static jn_status sgm_run_sync(jn_sgm* h, bool read_times, Queue queue) {
+  jn_sgm::Slot& s = h->slots[0];
+  if (s.pending) return JN_ERR_INVALID;                         // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(queue(s));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  HIP_TRY(hipGetLastError());
+  if (read_times) sgm_read_times(h, s);
+  return JN_OK;
+}
+
 extern "C" {
 
 void jn_sgm_params_default(jn_sgm_params* p) {
@@ -171,93 +184,68 @@ void jn_sgm_destroy(jn_sgm* h) {
   delete h;
 }
 
-jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t max_batch, int32_t device, jn_sgm** out) {
-  if (!p || !out || W < 8 || H < 8 || W > 8192 || H > 8192 || max_batch < 1) return JN_ERR_INVALID;
+void jn_sgm_cost_params_default(jn_sgm_cost_params* c) {
+  c->cost_function = JN_SGM_COST_BLOCK_SSD; c->block_radius = 2; c->cost_shift = 5; c->cost_max = 127;
+}
+
+// Every handle is made here; jn_sgm_create is the SAD3 case.  Refusals in the ABI's order, all before any device call: INVALID, UNSUPPORTED, NO_DEVICE.
+jn_status jn_sgm_create_cost(const jn_sgm_params* p, const jn_sgm_cost_params* c, int32_t W, int32_t H, int32_t max_batch, int32_t device, jn_sgm** out) {
+  if (!p || !c || !out || W < 8 || H < 8 || W > 8192 || H > 8192 || max_batch < 1) return JN_ERR_INVALID;
   *out = nullptr;
-  const int D = p->num_disparities;
-  if ((D != 64 && D != 128 && D != 256) || p->prefilter_cap < 1 || p->prefilter_cap > 31 || p->P1 < 0 || p->P2 < p->P1 ||
-      6 * p->prefilter_cap + p->P2 > 255)
-    return JN_ERR_UNSUPPORTED;
+  const int D = p->num_disparities, fn = c->cost_function;
+  const bool sad3 = fn == JN_SGM_COST_SAD3, ssd = fn == JN_SGM_COST_BLOCK_SSD, census = fn == JN_SGM_COST_CENSUS;
+  if (!sad3 && !ssd && !census && fn != JN_SGM_COST_EXTERNAL) return JN_ERR_UNSUPPORTED;
+  if ((D != 64 && D != 128 && D != 256) || p->prefilter_cap < 1 || p->prefilter_cap > 31 || p->P1 < 0 || p->P2 < p->P1) return JN_ERR_UNSUPPORTED;
+  // Every L_r <= max C + P2 must fit a byte (jn_sgm.h), side by side for the two kinds of cost:
+  //   computed (SAD3)   max C = 6 cap:            6 cap + P2 <= 255
+  //   a volume          max C = cost_max >= 1:    cost_max + P2 <= 255 where the handle makes the volume, and P2 <= 254 (room for a cost of 1) in
+  //                     any case: an EXTERNAL volume's bytes <= 255 - P2 are the caller's word
+  if (sad3 ? 6 * p->prefilter_cap + p->P2 > 255 : p->P2 > 254) return JN_ERR_UNSUPPORTED;
+  if ((ssd || census) && (c->block_radius < 2 || c->block_radius > 4 || c->cost_max < 1 || c->cost_max + p->P2 > 255)) return JN_ERR_UNSUPPORTED;
+  if (ssd && (c->cost_shift < 0 || c->cost_shift > 12)) return JN_ERR_UNSUPPORTED;   // (CENSUS: cost_shift is not used)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
   HIP_TRY(hipSetDevice(device));
   jn_sgm* h = new jn_sgm();
   h->p = *p; h->W = W; h->H = H; h->max_batch = max_batch; h->device = device;
-  jnav_sgm::sweep_geometry(W, H, D, p->P1, p->P2, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->sw, &h->sizes, max_batch);
+  if (sad3) jnav_sgm::sweep_geometry(W, H, D, p->P1, p->P2, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->sw, &h->sizes, max_batch);
+  else {
+    h->cost = *c;
+    jnav_sgm::sweep_geometry_cost(W, H, D, p->P1, p->P2, p->lr_max_diff, p->subpixel, &h->sw, &h->sizes, max_batch);
+    h->sw.cap = p->prefilter_cap;
+  }
+  if (ssd) jnav_bmq::geometry(W, H, D, c->block_radius, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->bq, &h->bqz, max_batch);
+  if (census) jnav_census::geometry(W, H, D, c->block_radius, &h->cq, &h->cqz, max_batch);
   const jn_status e = sgm_make_slot(h, 0);
   if (e != JN_OK) { jn_sgm_destroy(h); return e; }
   *out = h;
   return JN_OK;
 }
 
-void jn_sgm_cost_params_default(jn_sgm_cost_params* c) {
-  c->cost_function = JN_SGM_COST_BLOCK_SSD; c->block_radius = 2; c->cost_shift = 5; c->cost_max = 127;
-}
-
-jn_status jn_sgm_create_cost(const jn_sgm_params* p, const jn_sgm_cost_params* c, int32_t W, int32_t H, int32_t max_batch, int32_t device, jn_sgm** out) {
-  if (!p || !c || !out || W < 8 || H < 8 || W > 8192 || H > 8192 || max_batch < 1) return JN_ERR_INVALID;
-  *out = nullptr;
-  if (c->cost_function == JN_SGM_COST_SAD3) return jn_sgm_create(p, W, H, max_batch, device, out);
-  if (c->cost_function != JN_SGM_COST_BLOCK_SSD && c->cost_function != JN_SGM_COST_EXTERNAL && c->cost_function != JN_SGM_COST_CENSUS) return JN_ERR_UNSUPPORTED;
-  const int D = p->num_disparities;
-  if ((D != 64 && D != 128 && D != 256) || p->prefilter_cap < 1 || p->prefilter_cap > 31 || p->P1 < 0 || p->P2 < p->P1 || p->P2 > 254) return JN_ERR_UNSUPPORTED;
-  if (c->cost_function == JN_SGM_COST_BLOCK_SSD &&
-      (c->block_radius < 2 || c->block_radius > 4 || c->cost_shift < 0 || c->cost_shift > 12 || c->cost_max < 1 || c->cost_max + p->P2 > 255))
-    return JN_ERR_UNSUPPORTED;
-  if (c->cost_function == JN_SGM_COST_CENSUS && (c->block_radius < 2 || c->block_radius > 4 || c->cost_max < 1 || c->cost_max + p->P2 > 255))   // (cost_shift: not used)
-    return JN_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return JN_ERR_NO_DEVICE;
-  HIP_TRY(hipSetDevice(device));
-  jn_sgm* h = new jn_sgm();
-  h->p = *p; h->W = W; h->H = H; h->max_batch = max_batch; h->device = device; h->cost = *c;
-  jnav_sgm::sweep_geometry_cost(W, H, D, p->P1, p->P2, p->lr_max_diff, p->subpixel, &h->sw, &h->sizes, max_batch);
-  h->sw.cap = p->prefilter_cap;
-  if (c->cost_function == JN_SGM_COST_BLOCK_SSD) jnav_bmq::geometry(W, H, D, c->block_radius, p->prefilter_cap, p->lr_max_diff, p->subpixel, &h->bq, &h->bqz, max_batch);
-  if (c->cost_function == JN_SGM_COST_CENSUS) jnav_census::geometry(W, H, D, c->block_radius, &h->cq, &h->cqz, max_batch);
-  const jn_status e = sgm_make_slot(h, 0);
-  if (e != JN_OK) { jn_sgm_destroy(h); return e; }
-  *out = h;
-  return JN_OK;
+jn_status jn_sgm_create(const jn_sgm_params* p, int32_t W, int32_t H, int32_t max_batch, int32_t device, jn_sgm** out) {
+  const jn_sgm_cost_params sad3 = {JN_SGM_COST_SAD3, 0, 0, 0};
+  return jn_sgm_create_cost(p, &sad3, W, H, max_batch, device, out);
 }
 
 jn_status jn_sgm_cost_volume(jn_sgm* h, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride, uint8_t* dCost) {
   if (!h || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dCost || ((uintptr_t)dCost & 15) || pitch < h->W) return JN_ERR_INVALID;
   if (!h->makes_volume()) return JN_ERR_UNSUPPORTED;
-  jn_sgm::Slot& s = h->slots[0];
-  if (s.pending) return JN_ERR_INVALID;                         // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(sgm_queue_volume(h, s, n, dI1, dI2, pitch, (long long)image_stride, dCost));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  HIP_TRY(hipGetLastError());
-  return JN_OK;
+  return sgm_run_sync(h, false, [&](jn_sgm::Slot& s) { return sgm_queue_volume(h, s, n, dI1, dI2, pitch, (long long)image_stride, dCost); });
 }
 
 jn_status jn_sgm_aggregate_batch(jn_sgm* h, int32_t n, const uint8_t* dCost, int16_t* dDisp) {
   if (!h || n < 1 || n > h->max_batch || !dCost || ((uintptr_t)dCost & 15) || !dDisp) return JN_ERR_INVALID;
   if (h->cost.cost_function == JN_SGM_COST_SAD3) return JN_ERR_UNSUPPORTED;
-  jn_sgm::Slot& s = h->slots[0];
-  if (s.pending) return JN_ERR_INVALID;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-  HIP_TRY(jnav_sgm::sweep_run_cost(h->sw, n, dCost, dDisp, s.stream, s.sb, s.ev, true));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  HIP_TRY(hipGetLastError());
-  sgm_read_times(h, s);
-  return JN_OK;
+  return sgm_run_sync(h, true, [&](jn_sgm::Slot& s) {
+    const hipError_t e = hipEventRecord(s.ev[0], s.stream);
+    return e != hipSuccess ? e : jnav_sgm::sweep_run_cost(h->sw, n, dCost, dDisp, s.stream, s.sb, s.ev, true);
+  });
 }
 
 jn_status jn_sgm_process_batch(jn_sgm* h, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride, int16_t* dDisp) {
   if (!h || n < 1 || n > h->max_batch || !dI1 || !dI2 || !dDisp || pitch < h->W) return JN_ERR_INVALID;
   if (h->cost.cost_function == JN_SGM_COST_EXTERNAL) return JN_ERR_UNSUPPORTED;   // the handle only aggregates (jn_sgm_aggregate_batch)
-  jn_sgm::Slot& s = h->slots[0];
-  if (s.pending) return JN_ERR_INVALID;                         // slot 0's buffers carry a submitted batch: jn_sgm_wait(h, 0) first
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(sgm_queue(h, s, n, dI1, dI2, pitch, (long long)image_stride, dDisp, true, true));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  HIP_TRY(hipGetLastError());
-  sgm_read_times(h, s);
-  return JN_OK;
+  return sgm_run_sync(h, true, [&](jn_sgm::Slot& s) { return sgm_queue(h, s, n, dI1, dI2, pitch, (long long)image_stride, dDisp, true, true); });
 }
 
 jn_status jn_sgm_submit_scan(jn_sgm* h, int32_t slot, int32_t n, const uint8_t* dI1, const uint8_t* dI2, int32_t pitch, int64_t image_stride, int16_t* dDisp,

@@ -24,12 +24,12 @@ struct SweepBuffers {
   uint8_t* volH1;         // ... downwards
   uint32_t* gx;           // boundary columns handed from block to block [n][NB][H][3][4][D/8]; zeroed by the owner when allocated
   size_t gx_bytes;        // size of gx (all max_batch frames): what is zeroed when the tag wraps
-  uint32_t epoch;         // launches of k_sw_w on gx so far, modulo 2^16 (sweep_run advances it and zeroes gx when it wraps)
+  uint32_t epoch;         // launches of k_sw_w on gx so far, modulo 2^16 (every launch advances it; gx is zeroed when it wraps)
   uint32_t* flags;        // the ticket counters of the two row sweeps ([0] downward, [1] upward)
   uint32_t* minr;         // right-image winners [n][H][W] (S << 16 | d)
   uint32_t* dl;           // left winners [n][H][W] (d | d16 << 16), mirrored columns
   // The horizontal sweep and the downward sweep are independent (both read the prefiltered rows, they write different volumes): they run
-  // CONCURRENTLY, the horizontal one on this side stream (created by the first sweep_run, destroyed by sweep_release), forked and joined
+  // CONCURRENTLY, the horizontal one on this side stream (created by the first batch that forks, destroyed by sweep_release), forked and joined
   // with the two events.  One is bound by its volume writes, the other by issue and synchronisation: together they fill the GPU better.
   hipStream_t side;
   hipEvent_t ev_fork, ev_join;
@@ -48,7 +48,8 @@ hipError_t sweep_run(const SwDev& s, int n, const uint8_t* dI1, const uint8_t* d
 
 // The same sweeps over a byte cost volume (include/jn_sgm_cost.h): cost [n][H][W][D], natural column order, d ascending, every byte
 // <= 255 - P2.  sweep_geometry_cost lays the buffers out for them (gm is not used: the caller need not allocate it).  The caller records
-// ev[0] and queues the volume's producer on `st` first; ev[1..3] are recorded here, at the same places as sweep_run.
+// ev[0] and queues the volume's producer on `st` first; ev[1..3] are recorded here, at the same places as sweep_run: behind its prefilter both
+// calls queue the same sequence (k_swc_h in place of k_sw_h, k_sw_w reading `cost`); JN_SGM_OVERLAP does not apply.
 void sweep_geometry_cost(int W, int H, int D, int P1, int P2, int lr, int subpixel, SwDev* s, SweepSizes* z, int max_batch);
 hipError_t sweep_run_cost(const SwDev& s, int n, const uint8_t* cost, int16_t* dDisp, hipStream_t st, SweepBuffers& b, hipEvent_t* ev, bool side_overlap,
                           bool lr_kernel = true);

@@ -119,6 +119,19 @@ SGM_HOOKS_CASES = [(env, case(W, 24, D, "bits", 2, kw, why, edge=edge))
                                      ({"JN_SGM_LQ": "4"}, 256, 96))
                    for kw, edge, why in ((_HOOK_BYTE, ("top", "byte"), "byte form, 6 cap + P2 = 255"), (_HOOK_WIDE, ("top", "wide"), "16-bit form, 3 P2 = 258"))]
 
+# The sweeps over a cost volume (include/jn_sgm_cost.h: k_swc_h, k_sw_w<..., true>; four strips and the default lanes per pixel only).  They run in
+# tests/test_gpu_sgm_cost.py's anchor: jn_sgm.h's own cost as an EXTERNAL volume must give the plain handle's map, so the parameters lie inside both
+# handles' ranges (6 cap + P2 <= 255 is also "every byte of the volume <= 255 - P2").  The scene is the anchor's plane-and-box pair.
+_WIDE_VOL = {"P1": 7, "P2": 100, "prefilter_cap": 20}
+SGM_VOLUME_CASES = [case(W, H, D, min(D - 16, 48), 2, kw, why) for W, H, D, kw, why in (
+    (150, 60, 64, {}, "byte form, D = 64"),
+    (190, 45, 128, {"subpixel": 1}, "byte form, D = 128, 1/16 pixel"),
+    (300, 40, 256, {"subpixel": 1, "lr_max_diff": 2}, "byte form, eight lanes per pixel, 1/16 pixel"),
+    (141, 52, 64, _WIDE_VOL, "3 P2 > 255: the 16-bit three-path volume, D = 64"),
+    (333, 37, 128, {"lr_max_diff": -1}, "no L/R check"),
+    (222, 43, 128, _WIDE_VOL, "16-bit form, D = 128"),
+    (260, 36, 256, _WIDE_VOL, "16-bit form, eight lanes per pixel"))]
+
 DIRECTIONS = ((1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (-1, 1), (1, -1))
 DOWN, UP = ((0, 1), (1, 1), (-1, 1)), ((0, -1), (-1, -1), (1, -1))
 
@@ -224,20 +237,22 @@ BM_CASES = BM_SSD_CASES + BM_SAD_CASES
 
 
 # ------------------------------------------------------------------ dispatch, restated ------------------------------------------------------------------
-MATCHER_FAMILIES = ("k_sw_w", "k_sw_h", "k_bm", "k_bm_finish_sub", "k_bmq_match", "k_bmq_box", "k_bmq_finish")
+MATCHER_FAMILIES = ("k_sw_w", "k_sw_h", "k_swc_h", "k_bm", "k_bm_finish_sub", "k_bmq_match", "k_bmq_box", "k_bmq_finish")
 
 
-def sgm_instantiations(c, env=None):
-    """The k_sw_w / k_sw_h instantiations a batch of the SGM case launches (sgm_sweep.hip sweep_run, launch_w), named as c++filt prints them.
-    env: the hooks build's JN_SGM_NS / JN_SGM_LQ; the release library ignores both."""
-    env = env or {}
+def sgm_instantiations(c, env=None, volume=False):
+    """The k_sw_w and k_sw_h / k_swc_h instantiations a batch of the SGM case launches (sgm_sweep.hip sweep_run / sweep_run_cost, run_sweeps,
+    launch_w), named as c++filt prints them.  volume: the costs are read from a volume (the last argument of k_sw_w).
+    env: the hooks build's JN_SGM_NS / JN_SGM_LQ; the release library ignores both, and so does the volume path of either build."""
+    env = {} if volume or not env else env
     ns = int(env.get("JN_SGM_NS", 4))
     ns = ns if c.D != 256 and ns in (2, 8) else 4
     lq = 4 if c.D != 256 or env.get("JN_SGM_LQ") == "4" else 8
     nr = c.D // (2 * lq)                                      # disparity pairs per lane
     ring = 8 if nr <= 16 and lq == 4 else 4
     wide = "true" if 3 * c.kw.get("P2", 60) > 255 else "false"
-    return {"k_sw_h<%d, %d>" % (nr, lq)} | {"k_sw_w<%d, %d, %d, %s, %s, %d>" % (nr, ns, ring, final, wide, lq) for final in ("false", "true")}
+    return {"%s<%d, %d>" % ("k_swc_h" if volume else "k_sw_h", nr, lq)} | {
+        "k_sw_w<%d, %d, %d, %s, %s, %d, %s>" % (nr, ns, ring, final, wide, lq, "true" if volume else "false") for final in ("false", "true")}
 
 
 def bm_instantiations(c):
@@ -254,6 +269,8 @@ def table_instantiations():
         out |= sgm_instantiations(c)
     for env, c in SGM_HOOKS_CASES:
         out |= sgm_instantiations(c, env)
+    for c in SGM_VOLUME_CASES:
+        out |= sgm_instantiations(c, volume=True)
     for c in BM_CASES:
         out |= bm_instantiations(c)
     return out

@@ -1,5 +1,5 @@
 """The SGM mode over a cost volume (include/jn_sgm_cost.h) on the GPU, bit for bit against its definition (tests/sgm_cost_def.py): the
-block-SSD producer (k_sgc_volume), the sweeps that read a volume (k_swc_h / k_swc_w) tied to the ones that compute their cost, the two
+block-SSD producer (k_sgc_volume), the sweeps that read a volume (k_swc_h / k_sw_w<..., true>) tied to the ones that compute their cost, the two
 together, the pipelined slots with the scan tail, and the SAD3 handle."""
 import numpy as np
 import pytest
@@ -61,19 +61,13 @@ def test_cost_volume_equals_the_definition(jn, oracle, W, H, D, r, shift, cmax, 
         a.free()
 
 
-AGG_CASES = [
-    (150, 60, 64, dict()),
-    (190, 45, 128, dict(subpixel=1)),
-    (300, 40, 256, dict(subpixel=1, lr_max_diff=2)),
-    (141, 52, 64, dict(P1=7, P2=100, prefilter_cap=20)),          # 3 P2 > 255: the wide three-path volume
-    (333, 37, 128, dict(lr_max_diff=-1)),
-]
+AGG_CASES = [(c.W, c.H, c.D, c.kw) for c in mc.SGM_VOLUME_CASES]   # every k_swc_h / k_sw_w<..., true> form of the library (tests/test_matcher_matrix.py)
 
 
 @pytest.mark.parametrize("W,H,D,kw", AGG_CASES, ids=["%dx%d-D%d-%s" % (c[0], c[1], c[2], "+".join(sorted(c[3])) or "defaults") for c in AGG_CASES])
 def test_aggregating_the_sad3_volume_equals_the_plain_handle(jn, oracle, W, H, D, kw):
-    """The anchor that ties k_swc_* to k_sw_*: jn_sgm.h's own cost, built in numpy and brought as an EXTERNAL volume, must give the map
-    the plain handle computes from the images."""
+    """The anchor that ties k_swc_h / k_sw_w<..., true> to k_sw_h / k_sw_w<..., false>: jn_sgm.h's own cost, built in numpy and brought as an
+    EXTERNAL volume, must give the map the plain handle computes from the images."""
     DeviceArray = _dev(jn)
     n = 2
     pairs = [oracle.synth_pair(W, H, min(D - 16, 48), 500 + b) for b in range(n)]

@@ -32,9 +32,14 @@ def test_the_table_launches_every_matcher_kernel_in_the_library(jn):
     table = mc.table_instantiations()
     assert not binary - table, "in the library, launched by no case of tests/matcher_cases.py: %s" % sorted(binary - table)
     assert not table - binary, "the dispatch restated in tests/matcher_cases.py names kernels the library does not hold: %s" % sorted(table - binary)
-    # the release library ignores JN_SGM_NS / JN_SGM_LQ: what its cases reach is the twelve default forms of k_sw_w
+    # k_sw_w: 12 image forms are what the release library's cases reach (it ignores JN_SGM_NS / JN_SGM_LQ): D = 64, 128, 256 x downward / final x
+    # byte / 16-bit; 12 volume forms, the same product (the volume path has no JN_SGM_NS / JN_SGM_LQ forms); 44 in the binary: the image path's 8
+    # layouts (D = 64 and 128 with 2, 4, 8 strips, D = 256 with 8 and with 4 lanes per pixel) x 4 = 32, and the 12 volume forms
+    sw_w = lambda names, vol: [k for k in names if k.startswith("k_sw_w<") and k.endswith(", %s>" % vol)]
     release = set().union(*(mc.sgm_instantiations(c) for c in mc.SGM_CASES))
-    assert len([k for k in release if k.startswith("k_sw_w")]) == 12 and len([k for k in binary if k.startswith("k_sw_w")]) == 32
+    volume = set().union(*(mc.sgm_instantiations(c, volume=True) for c in mc.SGM_VOLUME_CASES))
+    assert len(sw_w(release, "false")) == 12 and len(sw_w(volume, "true")) == 12 and not sw_w(release, "true") and not sw_w(volume, "false")
+    assert len(sw_w(binary, "false")) == 32 and len(sw_w(binary, "true")) == 12 and len([k for k in binary if k.startswith("k_sw_w")]) == 44
 
 
 def test_the_hooks_build_holds_the_same_kernels(jn):
@@ -127,7 +132,7 @@ def test_bm_create_refuses_what_lies_outside_the_ranges(jn):
 
 def test_the_tables_parameters_are_inside_the_ranges():
     """every case is a valid call of the ABI (the GPU file shows they are ACCEPTED: P2 = 249, 6 cap + P2 = 255, D = 8)"""
-    for c in mc.SGM_CASES + [c for _, c in mc.SGM_HOOKS_CASES]:
+    for c in mc.SGM_CASES + [c for _, c in mc.SGM_HOOKS_CASES] + mc.SGM_VOLUME_CASES:       # (a volume case: 6 cap <= 255 - P2 bounds its bytes too)
         P1, P2, cap = c.kw.get("P1", 10), c.kw.get("P2", 60), c.kw.get("prefilter_cap", 31)
         assert c.D in (64, 128, 256) and 0 <= P1 <= P2 and 1 <= cap <= 31 and 6 * cap + P2 <= 255 and c.W >= 8 and c.H >= 8, c
     for c in mc.BM_CASES:
