@@ -18,6 +18,8 @@ from . import localmap  # noqa: F401
 from .localmap import LocalMap, LocalMapParams, Pose2D, LOCALMAP_EXPORTS, localmap_params  # noqa: F401
 from . import plan  # noqa: F401
 from .plan import Plan, PlanParams, PlanRecord, PlanCmd, PLAN_EXPORTS, plan_params  # noqa: F401
+from . import route  # noqa: F401
+from .route import Route, RouteParams, RouteStats, ROUTE_EXPORTS, route_params  # noqa: F401
 from . import postfilter  # noqa: F401
 from .postfilter import PostfilterParams, POSTFILTER_EXPORTS, postfilter_params, disparity_postfilter  # noqa: F401
 from . import ground, calib  # noqa: F401

@@ -26,8 +26,7 @@
 #include <new>
 #include <vector>
 #include "nav_tail.h"
-#include "dev_owner.h"
-#include "../../include/jn_plan.h"
+#include "plan_handle.h"
 
 namespace jnav {
 namespace {
@@ -36,7 +35,6 @@ constexpr int kFar = JN_CLEARANCE_FAR;
 constexpr int kClrBand = 8;                                                             // rows of d2 per workgroup
 constexpr int kClrThreads = 512;
 constexpr int kClrMaxWords = (kClrBand + 2 * JN_CLEARANCE_MAX_RADIUS + 31) / 32;        // 17: band + halo, in 32-row words
-constexpr double kPlMaxIndex = 1073741824.0;                                            // 2^30, as jn_localmap.h
 
 // grid [n][cy][cx] int8 -> d2 [n][cy][cx] u16.  gridDim = (ceil(cy / kClrBand), 1, n).  Bit i of a column's word w is row
 // y0 - R + 32 w + i; rows outside the grid are 0 bits (not obstacles).
@@ -119,7 +117,6 @@ struct PlDev {
   NavGrid c;
   int K, T, r2;
 };
-struct PlPose { double c, s, x, y; };             // cos / sin of theta taken on the host
 
 // tpl [T][K] (x_t, y_t); d2 [n][cells]; rec [n][K].  gridDim = (ceil(K / 256), n).
 __global__ void __launch_bounds__(256) k_plan_rollout(PlDev s, const PlPose* __restrict__ poses, const double2* __restrict__ tpl,
@@ -142,33 +139,6 @@ __global__ void __launch_bounds__(256) k_plan_rollout(PlDev s, const PlPose* __r
     last = cell;
   }
   rec[(size_t)frame * s.K + k] = jn_plan_record{t_end, t_hit, mn, last};
-}
-
-bool pl_pos(double v) { return std::isfinite(v) && v > 0.; }
-bool pl_nonneg(double v) { return std::isfinite(v) && v >= 0.; }
-
-bool pl_params_valid(const jn_plan_params* p) {
-  return p && pl_pos(p->v_max) && pl_pos(p->w_max) && pl_pos(p->horizon) && pl_nonneg(p->robot_radius) && pl_nonneg(p->w_goal) &&
-         pl_nonneg(p->w_clear) && pl_nonneg(p->w_speed) && pl_nonneg(p->clear_cap) && p->n_v >= 1 && p->n_v <= 16 && p->n_w >= 1 && p->n_w <= 65 &&
-         (p->n_w & 1) && p->steps >= 1 && p->steps <= 128 && p->reserved == 0;
-}
-// the resolution, and the robot's radius in cells (r2 must stay below the "far" value)
-bool pl_resolution_valid(const jn_plan_params* p, double res) { return pl_pos(res) && p->robot_radius / res <= (double)JN_CLEARANCE_MAX_RADIUS; }
-bool pl_coord_valid(double v, double res) { return std::isfinite(v) && std::fabs(v / res) <= kPlMaxIndex; }
-bool pl_pose_valid(const jn_pose2d& q, double res) { return pl_coord_valid(q.x, res) && pl_coord_valid(q.y, res) && std::isfinite(q.theta); }
-
-// jn_plan.h "candidates" and "template": every operation on its own
-void pl_candidate(const jn_plan_params& p, int k, double& v, double& w) {
-  const int iv = k / p.n_w, iw = k - iv * p.n_w, m = (p.n_w - 1) / 2;
-  v = (p.v_max * (double)(iv + 1)) / (double)p.n_v;
-  w = m == 0 ? 0. : (p.w_max * (double)(iw - m)) / (double)m;
-}
-void pl_point(const jn_plan_params& p, double v, double w, int s, double& x, double& y) {
-  const double t = (p.horizon * (double)(s + 1)) / (double)p.steps;
-  if (w == 0.) { x = v * t; y = 0.; return; }
-  const double r = v / w, a = w * t;
-  x = r * std::sin(a);
-  y = r * (1. - std::cos(a));
 }
 
 // jn_plan.h "choice" of one frame; c / s: the pose's cosine and sine
@@ -196,30 +166,8 @@ void pl_choose(const jn_plan_params& p, double res, const jn_plan_record* rec, d
 }
 
 }  // namespace
-}  // namespace jnav
 
-using namespace jnav;
-
-struct jn_plan {
-  jn_plan_params p;
-  double res = 0.;
-  int cx = 0, cy = 0, K = 0, r2 = 0, device = 0, max_batch = 0;
-  DevOwner own;
-  double2* d_tpl = nullptr;            // [steps][K]
-  PlPose* d_poses = nullptr;           // [max_batch]
-  PlPose* h_poses = nullptr;           // pinned
-  jn_plan_record* d_rec = nullptr;     // [max_batch][K]
-  jn_plan_record* h_rec = nullptr;     // pinned
-};
-
-namespace {
-
-void pl_free(jn_plan* h) {
-  h->own.release();
-  delete h;
-}
-
-// the arguments of evaluate / command that do not depend on the output
+// plan_handle.h: the arguments of evaluate / command that do not depend on the output
 bool pl_call_valid(const jn_plan* h, int n, const uint16_t* dD2, const double* origin, const jn_pose2d* poses) {
   if (!h || !dD2 || !origin || !poses || n < 1 || n > h->max_batch) return false;
   if (!pl_coord_valid(origin[0], h->res) || !pl_coord_valid(origin[1], h->res)) return false;
@@ -228,8 +176,8 @@ bool pl_call_valid(const jn_plan* h, int n, const uint16_t* dD2, const double* o
   return true;
 }
 
-// the rollout of n frames into h->h_rec; the poses' cosines and sines stay in h->h_poses
-jn_status pl_evaluate(jn_plan* h, int n, const uint16_t* dD2, const double* origin, const jn_pose2d* poses) {
+// plan_handle.h: the rollout of n frames on the null stream, the records on their way into h->h_rec
+jn_status pl_enqueue(jn_plan* h, int n, const uint16_t* dD2, const double* origin, const jn_pose2d* poses) {
   for (int f = 0; f < n; f++) h->h_poses[f] = PlPose{std::cos(poses[f].theta), std::sin(poses[f].theta), poses[f].x, poses[f].y};
   HIP_TRY(hipSetDevice(h->device));
   PlDev s;
@@ -238,6 +186,24 @@ jn_status pl_evaluate(jn_plan* h, int n, const uint16_t* dD2, const double* orig
   HIP_TRY(hipMemcpyAsync(h->d_poses, h->h_poses, sizeof(PlPose) * (size_t)n, hipMemcpyHostToDevice, nullptr));
   hipLaunchKernelGGL(k_plan_rollout, dim3((unsigned)((h->K + 255) / 256), (unsigned)n), dim3(256), 0, nullptr, s, h->d_poses, h->d_tpl, dD2, h->d_rec);
   HIP_TRY(hipMemcpyAsync(h->h_rec, h->d_rec, sizeof(jn_plan_record) * (size_t)n * h->K, hipMemcpyDeviceToHost, nullptr));
+  return JN_OK;
+}
+
+}  // namespace jnav
+
+using namespace jnav;
+
+namespace {
+
+void pl_free(jn_plan* h) {
+  h->own.release();
+  delete h;
+}
+
+// the rollout of n frames into h->h_rec; the poses' cosines and sines stay in h->h_poses
+jn_status pl_evaluate(jn_plan* h, int n, const uint16_t* dD2, const double* origin, const jn_pose2d* poses) {
+  const jn_status e = pl_enqueue(h, n, dD2, origin, poses);
+  if (e != JN_OK) return e;
   HIP_TRY(hipStreamSynchronize(nullptr));
   HIP_TRY(hipGetLastError());
   return JN_OK;
