@@ -71,7 +71,8 @@ def test_other_scenes_bit_exact_vs_oracle(jn, oracle, same, kind):
 
 def test_full_hd_and_wide_images(jn, oracle, same):
     """BASELINE config 5's frame (1920x1080, disparity range 256: the widest LDS windows) and an image wider than
-    2560 px, which takes the global-memory support-matching kernel instead of the LDS one."""
+    2560 px: since lattice rows are cut into segments it stays in the LDS kernel and the plane flow (eight segments of 65 candidates, windows of
+    459 columns in the 640 bucket); the global-memory kernel k_support runs in tests/test_gpu_elas_matrix.py (JN_SUPPORT_SEGMENTS=1, hooks build)."""
     for (W, H, sd, dmax, seed) in ((1920, 1080, 256, 255, 12345), (2600, 200, 40, 63, 3)):
         L, R = jn.node.synth_pair(W, H, sd, seed)
         st, D1, D2 = run_elas(jn, jn.Elas.parameters(0, disp_max=dmax), L, R)
