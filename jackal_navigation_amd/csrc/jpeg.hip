@@ -18,26 +18,34 @@
 namespace {
 
 // ---- dequantisation + 8x8 inverse DCT ("slow integer" form) + range limit: 8 lanes per block ----
-#define JDESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
+// libjpeg forms these sums in a C long (64 bits on the hosts OpenCV runs on), keeps the pass-1 workspace in int and takes the result
+// modulo 1024 (range_limit).  ACC is the type the sums are formed in, SH its signed twin for the arithmetic descale:
+//   pass 1: long long — a dequantised coefficient of a legal file (16-bit coefficient x 8- or 16-bit quantiser) times a 15-bit constant
+//           does not fit 32 bits (1023 x 255 already does not), and a bit lost here reaches the pixel through pass 2's products;
+//   pass 2: unsigned / int — only bits 18..27 of the sum reach the pixel, so sums modulo 2^32 are exact for what is kept, and unsigned
+//           arithmetic makes the wrap defined.
+template <typename ACC, typename SH>
 __device__ __forceinline__ void idct_1d(const int in[8], int out[8], int shift) {
+  auto K = [](int c) { return (ACC)c; };
+  auto descale = [&](ACC x) { return (int)((SH)(x + ((ACC)1 << (shift - 1))) >> shift); };
   // even part
-  int z2 = in[2], z3 = in[6];
-  int z1 = (z2 + z3) * 4433;
-  int tmp2 = z1 + z3 * (-15137), tmp3 = z1 + z2 * 6270;
-  int tmp0 = (in[0] + in[4]) * 8192, tmp1 = (in[0] - in[4]) * 8192;            // << CONST_BITS
-  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  ACC z2 = (ACC)in[2], z3 = (ACC)in[6];
+  ACC z1 = (z2 + z3) * K(4433);
+  ACC tmp2 = z1 + z3 * K(-15137), tmp3 = z1 + z2 * K(6270);
+  ACC tmp0 = ((ACC)in[0] + (ACC)in[4]) * K(8192), tmp1 = ((ACC)in[0] - (ACC)in[4]) * K(8192);            // << CONST_BITS
+  const ACC tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
   // odd part
-  tmp0 = in[7]; tmp1 = in[5]; tmp2 = in[3]; tmp3 = in[1];
-  z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2; int z4 = tmp1 + tmp3;
-  const int z5 = (z3 + z4) * 9633;
-  tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;
-  z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
+  tmp0 = (ACC)in[7]; tmp1 = (ACC)in[5]; tmp2 = (ACC)in[3]; tmp3 = (ACC)in[1];
+  z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2; ACC z4 = tmp1 + tmp3;
+  const ACC z5 = (z3 + z4) * K(9633);
+  tmp0 *= K(2446); tmp1 *= K(16819); tmp2 *= K(25172); tmp3 *= K(12299);
+  z1 *= K(-7373); z2 *= K(-20995); z3 *= K(-16069); z4 *= K(-3196);
   z3 += z5; z4 += z5;
   tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-  out[0] = JDESCALE(tmp10 + tmp3, shift); out[7] = JDESCALE(tmp10 - tmp3, shift);
-  out[1] = JDESCALE(tmp11 + tmp2, shift); out[6] = JDESCALE(tmp11 - tmp2, shift);
-  out[2] = JDESCALE(tmp12 + tmp1, shift); out[5] = JDESCALE(tmp12 - tmp1, shift);
-  out[3] = JDESCALE(tmp13 + tmp0, shift); out[4] = JDESCALE(tmp13 - tmp0, shift);
+  out[0] = descale(tmp10 + tmp3); out[7] = descale(tmp10 - tmp3);
+  out[1] = descale(tmp11 + tmp2); out[6] = descale(tmp11 - tmp2);
+  out[2] = descale(tmp12 + tmp1); out[5] = descale(tmp12 - tmp1);
+  out[3] = descale(tmp13 + tmp0); out[4] = descale(tmp13 - tmp0);
 }
 __device__ __forceinline__ uint8_t range_limit(int x) {      // IJG sample range table, indexed modulo 1024 around +128
   const int i = x & 1023;
@@ -55,7 +63,7 @@ __global__ void __launch_bounds__(256) k_jpeg_idct_gray(const int16_t* __restric
     const int16_t* c = coef + (size_t)block * 64;
 #pragma unroll
     for (int r = 0; r < 8; r++) col[r] = (int)c[8 * r + l] * (int)qt.q[8 * r + l];     // column l, dequantised
-    idct_1d(col, tmp, 13 - 2);                                                          // pass 1: CONST_BITS - PASS1_BITS
+    idct_1d<long long, long long>(col, tmp, 13 - 2);                                    // pass 1: CONST_BITS - PASS1_BITS
 #pragma unroll
     for (int r = 0; r < 8; r++) ws[lb][8 * r + l] = tmp[r];
   }
@@ -63,7 +71,7 @@ __global__ void __launch_bounds__(256) k_jpeg_idct_gray(const int16_t* __restric
   if (!in) return;
 #pragma unroll
   for (int k = 0; k < 8; k++) col[k] = ws[lb][8 * l + k];                               // row l of the workspace
-  idct_1d(col, tmp, 13 + 2 + 3);                                                        // pass 2: CONST_BITS + PASS1_BITS + 3
+  idct_1d<unsigned, int>(col, tmp, 13 + 2 + 3);                                         // pass 2: CONST_BITS + PASS1_BITS + 3
   const int bx = block % bw, by = block / bw;
   const int y = by * 8 + l;
   if (y >= H) return;

@@ -220,13 +220,18 @@ __global__ void __launch_bounds__(256) k_remap(const uint8_t* __restrict__ src, 
                                                uint8_t* __restrict__ dst, int W, int H, int dpitch, long long dstride) {
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, img = blockIdx.z;
   if (x >= W) return;
-  const int sx = (int)rintf(__fmul_rn(mapx[(size_t)y * W + x], 32.0f)), sy = (int)rintf(__fmul_rn(mapy[(size_t)y * W + x], 32.0f));
+  const float qx = rintf(__fmul_rn(mapx[(size_t)y * W + x], 32.0f)), qy = rintf(__fmul_rn(mapy[(size_t)y * W + x], 32.0f));
+  uint8_t* out = dst + (long long)img * dstride + (size_t)y * dpitch + x;
+  // NaN (what k_undistort_map writes where _w == 0), or a 1/32-pixel value outside int32: outside every image, the border value.
+  // The conversion alone would turn NaN into 0, i.e. into source pixel (0, 0).
+  if (!(qx >= -2147483648.0f && qx < 2147483648.0f && qy >= -2147483648.0f && qy < 2147483648.0f)) { *out = 0; return; }
+  const int sx = (int)qx, sy = (int)qy;
   const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
   const uint8_t* S = src + (long long)img * sstride;
   auto tap = [&](int xx, int yy) -> int { return (xx >= 0 && xx < sw && yy >= 0 && yy < sh) ? S[(size_t)yy * spitch + xx] : 0; };
   const int p00 = tap(ix, iy), p01 = tap(ix + 1, iy), p10 = tap(ix, iy + 1), p11 = tap(ix + 1, iy + 1);
   const int acc = (32 - fx) * (32 - fy) * p00 + fx * (32 - fy) * p01 + (32 - fx) * fy * p10 + fx * fy * p11;
-  dst[(long long)img * dstride + (size_t)y * dpitch + x] = (uint8_t)((acc + 512) >> 10);
+  *out = (uint8_t)((acc + 512) >> 10);
 }
 
 // Point cloud (-g, point_cloud.cpp:321-352): column-major order (i outer, j inner) with d >= 2.

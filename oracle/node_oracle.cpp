@@ -214,7 +214,11 @@ extern "C" void orc_remap_bilinear(const uint8_t* src, int32_t sw, int32_t sh, i
                                    uint8_t* dst, int32_t W, int32_t H, int32_t dpitch) {
   for (int y = 0; y < H; y++)
     for (int x = 0; x < W; x++) {
-      const int sx = (int)std::nearbyintf(mapx[(size_t)y * W + x] * 32.0f), sy = (int)std::nearbyintf(mapy[(size_t)y * W + x] * 32.0f);
+      const float qx = std::nearbyintf(mapx[(size_t)y * W + x] * 32.0f), qy = std::nearbyintf(mapy[(size_t)y * W + x] * 32.0f);
+      // a coordinate that is NaN or whose 1/32-pixel value leaves int32 is outside every image: the border value (what cvRound's
+      // INT_MIN comes to in OpenCV on x86) — decided on the float, so that no out-of-range value is ever cast
+      if (!(qx >= -2147483648.0f && qx < 2147483648.0f && qy >= -2147483648.0f && qy < 2147483648.0f)) { dst[(size_t)y * dpitch + x] = 0; continue; }
+      const int sx = (int)qx, sy = (int)qy;
       const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
       auto tap = [&](int xx, int yy) -> int { return (xx >= 0 && xx < sw && yy >= 0 && yy < sh) ? src[(size_t)yy * spitch + xx] : 0; };
       const int acc = (32 - fx) * (32 - fy) * tap(ix, iy) + fx * (32 - fy) * tap(ix + 1, iy) + (32 - fx) * fy * tap(ix, iy + 1) +

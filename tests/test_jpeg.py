@@ -2,7 +2,7 @@
 
 Third-party arithmetic (libjpeg via OpenCV) pinned by Pillow / libjpeg-turbo fixtures
 (tests/golden/jpeg_cases.npz, tests/golden/make_jpeg_golden.py).  Here: marker parsing and Huffman decoding through the
-host hook jn_host_jpeg_coefficients, with the inverse DCT restated in numpy (the IJG "slow integer" definition) so that
+host hook jn_host_jpeg_coefficients, with the inverse DCT restated in numpy (tests/jpeg_def.py, the IJG "slow integer" definition) so that
 the whole chain can be compared with the fixtures without a GPU; tests/test_gpu_round2.py runs the kernel."""
 import ctypes as C
 import hashlib
@@ -11,6 +11,10 @@ import os
 import numpy as np
 import pytest
 
+import frontend_cases as fc
+import jpeg_write
+from jpeg_def import decode, islow_idct, range_limit
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -18,34 +22,6 @@ def cases():
     z = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_cases.npz"))
     names = sorted({k.split("__")[0] for k in z.files})
     return z, names
-
-
-def islow_idct(block):
-    """8x8 IJG slow-integer inverse DCT of one dequantised block (int64 numpy, exact), result before range limiting."""
-    def one_d(v, shift):
-        z2, z3 = v[2], v[6]
-        z1 = (z2 + z3) * 4433
-        tmp2 = z1 + z3 * (-15137); tmp3 = z1 + z2 * 6270
-        tmp0 = (v[0] + v[4]) << 13; tmp1 = (v[0] - v[4]) << 13
-        tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
-        t0, t1, t2, t3 = v[7], v[5], v[3], v[1]
-        z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2; z4 = t1 + t3
-        z5 = (z3 + z4) * 9633
-        t0 = t0 * 2446; t1 = t1 * 16819; t2 = t2 * 25172; t3 = t3 * 12299
-        z1 = z1 * -7373; z2 = z2 * -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5
-        t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4
-        r = 1 << (shift - 1)
-        return [(tmp10 + t3 + r) >> shift, (tmp11 + t2 + r) >> shift, (tmp12 + t1 + r) >> shift, (tmp13 + t0 + r) >> shift,
-                (tmp13 - t0 + r) >> shift, (tmp12 - t1 + r) >> shift, (tmp11 - t2 + r) >> shift, (tmp10 - t3 + r) >> shift]
-    b = block.astype(np.int64)
-    ws = np.stack(one_d([b[r] for r in range(8)], 11))            # pass 1 works on columns: element r of every column at once
-    out = np.stack(one_d([ws[:, k] for k in range(8)], 18), axis=1)
-    return out
-
-
-def range_limit(x):
-    i = x & 1023
-    return np.where(i < 128, 128 + i, np.where(i < 512, 255, np.where(i < 896, 0, i - 896))).astype(np.uint8)
 
 
 def host_decode(jn, data):
@@ -63,7 +39,7 @@ def host_decode(jn, data):
     img = np.zeros((bh.value * 8, bw.value * 8), np.uint8)
     for by in range(bh.value):
         for bx in range(bw.value):
-            img[8 * by:8 * by + 8, 8 * bx:8 * bx + 8] = range_limit(islow_idct(blocks[by, bx]))
+            img[8 * by:8 * by + 8, 8 * bx:8 * bx + 8] = range_limit(islow_idct(blocks[by, bx], fits_int32=False))   # any file, fuzzed ones too: exact, no condition
     return 0, img[:h.value, :w.value]
 
 
@@ -160,3 +136,82 @@ def test_fuzzed_files_never_crash_the_host_decoder(jn):
         outcomes[st] = outcomes.get(st, 0) + 1
     assert set(outcomes) <= {0, 2, 3, 5}, outcomes
     assert outcomes.get(3, 0) > 50, outcomes
+
+
+def host_coefficients(jn, data):
+    L = jn.load()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    q = (C.c_uint16 * 64)()
+    w, h, bw, bh = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    n = L.jn_host_jpeg_coefficients(buf.ctypes.data, buf.size, None, 0, q, C.byref(w), C.byref(h), C.byref(bw), C.byref(bh))
+    assert n == bw.value * bh.value * 64, n
+    coef = np.zeros(n, np.int16)
+    assert L.jn_host_jpeg_coefficients(buf.ctypes.data, buf.size, coef.ctypes.data, n, q, C.byref(w), C.byref(h), C.byref(bw), C.byref(bh)) == n
+    return coef.reshape(bh.value, bw.value, 8, 8), np.array(list(q)).reshape(8, 8), w.value, h.value
+
+
+def test_written_coefficients_come_back_from_the_entropy_decoder(jn):
+    """tests/jpeg_write.py -> jn_host_jpeg_coefficients: exactly the coefficients, the table and the frame size that were written, for
+    every synthetic frame of frontend_cases.jpeg_frames (the frames tests/test_gpu_frontend.py hands to the GPU's inverse DCT)."""
+    frames = fc.jpeg_frames()
+    assert {(W, H) for _, W, H, _, _, _ in frames} == set(fc.JPEG_SIZES)
+    for name, W, H, quant, coef, _ in frames:
+        got, q, w, h = host_coefficients(jn, jpeg_write.write_gray(coef, quant, W, H))
+        assert (w, h) == (W, H), name
+        assert np.array_equal(q, quant), name
+        assert np.array_equal(got, coef), name
+
+
+def test_synthetic_blocks_reach_every_branch_of_the_range_limit_within_int32():
+    """The reference alone, on the CPU.  Every block of the q1 and dense pools passes jpeg_def's int32 assertion (none is dropped);
+    every block of the q255 pool fails it (1023 * 255 needs more than 32 bits at every position, frontend_cases.jpeg_pools).
+    The dense pool spreads past +-1500 before range limiting, and over all pools each of range_limit's four branches and the wrap
+    beyond +512 and beyond -512 (where the table's answer is not the clamp's) is hit."""
+    pre = {}
+    for name, quant, blocks, fits in fc.jpeg_pools():
+        if fits:
+            pre[name] = np.array([islow_idct(b * quant) for b in blocks])                 # asserts int32 for each block
+        else:
+            pre[name] = np.array([islow_idct(b * quant, fits_int32=False) for b in blocks])
+            for b in blocks[6:]:                                                          # the singles (the first six are DC alone)
+                with pytest.raises(AssertionError):
+                    islow_idct(b * quant)
+    assert pre["dense"].min() <= -1500 and pre["dense"].max() >= 1500
+    assert np.percentile(pre["dense"], 5) < -1500 and np.percentile(pre["dense"], 95) > 1500    # spread, not two outliers
+    x = np.concatenate([p.ravel() for p in pre.values()])
+    i = x & 1023
+    for hit in (i < 128, (i >= 128) & (i < 512), (i >= 512) & (i < 896), i >= 896):
+        assert hit.any()
+    d = pre["dense"].ravel()                                      # the wrap is reached by blocks that fit int32, not by q255 alone
+    clamp = np.clip(d + 128, 0, 255)
+    for beyond in (d >= 512, d < -512):
+        assert (range_limit(d)[beyond] != clamp[beyond]).any()
+
+
+def test_pillow_decodes_written_files_like_the_definition(jn):
+    """When Pillow imports: libjpeg-turbo's decode of a written file equals jpeg_def for blocks whose dequantised values stay within
+    +-1024 and whose results stay within the range table's unwrapped span (-512 <= x < 512; two coefficients per block keep them
+    there: 2 * 1024 * 0.2405 < 512).  Extreme blocks are not pinned against it: its SIMD inverse DCT works in 16 bits and
+    saturates where the table wraps."""
+    Image = pytest.importorskip("PIL.Image")
+    import io
+    rng = np.random.default_rng(8)
+    peak = 0
+    for k, (W, H) in enumerate(fc.JPEG_SIZES + ((35, 21),)):
+        bw, bh = (W + 7) // 8, (H + 7) // 8
+        quant = rng.integers(1, 17, (8, 8))
+        coef = np.zeros((bh * bw, 64), np.int64)
+        for b in coef:
+            for pos in rng.integers(0, 64, 2):
+                b[pos] = rng.integers(-1024, 1025) // quant.ravel()[pos]
+        coef = coef.reshape(bh, bw, 8, 8)
+        assert np.abs(coef * quant).max() <= 1024 and np.abs(decode(coef, quant, W, H)[1]).max() < 512
+        peak = max(peak, np.abs(coef * quant).max())
+        data = jpeg_write.write_gray(coef, quant, W, H)
+        im = Image.open(io.BytesIO(data)); im.load()
+        assert im.mode == "L" and im.size == (W, H)
+        img, _ = decode(coef, quant, W, H)
+        assert np.array_equal(np.asarray(im), img), (W, H)
+        st, ours = host_decode(jn, np.frombuffer(data, np.uint8))
+        assert st == 0 and np.array_equal(ours, img)
+    assert peak > 1000

@@ -1,8 +1,12 @@
 """Rectification front end: stereoRectify / initUndistortRectifyMap / remap.
 The arithmetic lives in OpenCV, which is neither in the reference tree nor installed: parity is
-UNPINNED, so these tests check geometry (CPU) and GPU-vs-oracle agreement (gpu)."""
+UNPINNED, so these tests check geometry (CPU) and GPU-vs-oracle agreement (gpu); tests/frontend_def.py is the independent numpy
+definition of the map and of remap, tests/test_gpu_frontend.py holds the kernels against it at the edges."""
 import numpy as np
 import pytest
+
+import frontend_cases as fc
+import frontend_def as fd
 
 
 def _mats(r):
@@ -70,6 +74,78 @@ def test_map_and_remap_oracle_properties(oracle):
     assert (oracle.remap(src, mx + 500, my) == 0).all()
 
 
+def test_map_definition_equals_the_oracle_bit_for_bit(jn, oracle, same):
+    """frontend_def.undistort_map (numpy float64, one rounded operation at a time) == oracle.undistort_map on the float32 bits: the
+    shipped rig's two eyes and the synthetic calibrations at every size the GPU test uses."""
+    from jackal_navigation_amd import node
+    for W, H in fc.MAP_SIZES:
+        for cal in fc.shipped_calibrations(node, W, H) + fc.synthetic_calibrations():
+            mx, my = fd.undistort_map(*cal, W, H)
+            mxo, myo = oracle.undistort_map(*cal, W, H)
+            assert same(mx, mxo) and same(my, myo), (W, H, cal[0])
+
+
+# Contractions of a * b + c (frontend_def.FMA_SITES) that the cancelling maps must expose, each in at least one map.  Measured over the
+# 48 maps: ray_x_j 9, ray_y_i 10, u_xkr 7, v_ykr 11, u_fx 48, v_fy 48.  The other sites feed terms far below the result's last bit
+# (p1, p2 and the k polynomial contribute ~1e-4 of it; i * iR[1] next to j * iR[0] in x, and the w row, likewise) and show in 0 or 1 map.
+VISIBLE_FMA_SITES = ("ray_x_j", "ray_y_i", "u_xkr", "v_ykr", "u_fx", "v_fy")
+
+
+def test_cancelling_maps_are_zero_and_expose_a_contracted_multiply_add(oracle, same):
+    """frontend_cases.cancelling_calibrations: the definition and the oracle agree bit for bit and give exactly 0.0 at the tuned pixel;
+    a formula with ONE multiply-add contracted to an fma (frontend_def.undistort_pixel, exact rational fma) gives a float32 other
+    than 0 there — for each site of VISIBLE_FMA_SITES in at least one map, for the final fx * t + u0 and fy * t + v0 in every map.
+    So the bit-equality tests of the kernel (tests/test_gpu_frontend.py) fail for a kernel compiled or rewritten with contraction."""
+    cases = fc.cancelling_calibrations()
+    seen = {s: 0 for s in fd.FMA_SITES}
+    for K, D, R, P, W, H in cases:
+        mx, my = fd.undistort_map(K, D, R, P, W, H)
+        mxo, myo = oracle.undistort_map(K, D, R, P, W, H)
+        assert same(mx, mxo) and same(my, myo)
+        assert mx[-1, -1] == 0 and my[-1, -1] == 0 and abs(mx[-1, -2]) > 0.5 and abs(my[-2, -1]) > 0.5
+        assert fd.undistort_pixel(K, D, R, P, W - 1, H - 1) == (0.0, 0.0)
+        u, v = fd.undistort_pixel(K, D, R, P, W - 2, H - 2)                  # the scalar form is the vector form
+        assert np.float32(u) == mx[-2, -2] and np.float32(v) == my[-2, -2]
+        for s in fd.FMA_SITES:
+            u, v = fd.undistort_pixel(K, D, R, P, W - 1, H - 1, s)
+            seen[s] += bool(np.float32(u) != 0 or np.float32(v) != 0)
+    assert all(seen[s] >= 1 for s in VISIBLE_FMA_SITES), seen
+    assert seen["u_fx"] == seen["v_fy"] == len(cases) == 48, seen
+
+
+def test_direct_column_term_equals_opencvs_walk_on_the_shipped_rig(jn, same):
+    """OpenCV accumulates the column term of the ray (`_x += ir[0]` once per pixel); the kernel and the oracle evaluate j * iR[0].
+    On the shipped calibration, both eyes, at 320x180, 333x187, 640x360 and 1280x720 the two give the same float32 maps, bit for bit.
+    This is a MEASURED property of this rig at these sizes, not a theorem: the doubles differ in their last bits and the float
+    rounding absorbs that here; tests/frontend_cases.py's synthetic calibrations already differ in a few entries at 1280x720."""
+    from jackal_navigation_amd import node
+    for W, H in fc.WALK_SIZES:
+        for cal in fc.shipped_calibrations(node, W, H):
+            mx, my = fd.undistort_map(*cal, W, H)
+            wx, wy = fd.undistort_map(*cal, W, H, walk=True)
+            assert same(mx, wx) and same(my, wy), (W, H)
+
+
+def test_remap_definition_equals_the_oracle_on_every_hand_built_map(oracle, same):
+    """frontend_def.remap == oracle.remap, exactly, on every map of frontend_cases.remap_cases (the ones the GPU test runs): phases,
+    borders and corners, negative fractions and ties, sources of one and two pixels, unrepresentable coordinates."""
+    cases = fc.remap_cases()
+    assert len(cases) == len(fc.SRC_SIZES) * len(fc.DST_SIZES) + 1 + len(fc.SRC_SIZES) + 2 + 2
+    for name, src, mx, my in cases:
+        assert same(fd.remap(src, mx, my), oracle.remap(src, mx, my)), name
+        if name.startswith("unrepresentable"):
+            bad = ~(fd.fixed_point(mx)[1] & fd.fixed_point(my)[1])
+            assert src[0, 0] != 0 and bad.sum() >= len(fc.UNREPRESENTABLE) * 7 and (fd.remap(src, mx, my)[bad] == 0).all()
+            assert (fd.remap(src, mx, my) == src[0, 0]).any()           # the representable neighbours do land on pixel (0, 0)
+    # what the definition itself must get right, spelled out: ties to even, floor semantics below zero, the border
+    src = np.array([[200, 100]], np.uint8)
+    one = lambda x, y: int(fd.remap(src, np.array([[x]], np.float32), np.array([[y]], np.float32))[0, 0])   # noqa: E731
+    assert one(-1 / 64, 0) == 200                    # -0.5 -> 0 (even), not -1
+    assert one(-3 / 64, 0) == (30 * 32 * 0 + 2 * 32 * 0 + 30 * 32 * 200 + 512) >> 10        # -1.5 -> -2: ix -1, fx 30
+    assert one(1 / 64, 0) == 200 and one(3 / 64, 0) == (30 * 32 * 200 + 2 * 32 * 100 + 512) >> 10       # 0.5 -> 0, 1.5 -> 2
+    assert one(-0.5, 0) == 100 and one(-1, 0) == 0 and one(1.5, 0) == 50 and one(0, -0.5) == 100
+
+
 @pytest.mark.gpu
 def test_maps_and_remap_gpu_vs_oracle(jn, oracle, same):
     from jackal_navigation_amd import node
@@ -85,7 +161,7 @@ def test_maps_and_remap_gpu_vs_oracle(jn, oracle, same):
         mx, my = node.init_undistort_rectify_map(list(K), list(D), list(R), list(P), W, H)
         mxo, myo = oracle.undistort_map(list(K), list(D), list(R), list(P), W, H)
         gx, gy = mx.numpy(), my.numpy()
-        assert np.abs(gx - mxo).max() <= 2e-4 and np.abs(gy - myo).max() <= 2e-4     # same doubles up to the last float ulp
+        assert same(gx, mxo) and same(gy, myo)        # the kernel is all __d*_rn, the oracle is built without contraction: the same bits
         ddst = DeviceArray((n, H, W), np.uint8)
         node.remap(n, dsrc.ptr, c.calib_width, c.calib_height, c.calib_width, c.calib_width * c.calib_height, mx.ptr, my.ptr,
                    ddst.ptr, W, H, W, W * H)
