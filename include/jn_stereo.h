@@ -164,6 +164,8 @@ void jn_scan_params_default(jn_scan_params* sp, int32_t width, int32_t height);
 #define JN_SCAN_EMPTY 1e9   /* `INF` of point_cloud.cpp:54: value of a bin no pixel fell into */
 
 /* leftdpf.convertTo(show, CV_8U, 1.) (point_cloud.cpp:422): round-half-even, saturate; -10 -> 0.
+ * NaN gives 0, +inf 255 and -inf 0: ELAS never emits them, and the reference does not define cv::convertTo's
+ * answer for non-finite values, so these are this library's own (tests/test_gpu_rigs.py pins them).
  * Device pointers, n elements. */
 jn_status jn_disparity_to_u8(int32_t device, const float* dD, uint8_t* dOut, int64_t n);
 
