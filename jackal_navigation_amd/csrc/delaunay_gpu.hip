@@ -18,7 +18,7 @@
 //   * 16-bit everything: handles (triangle << 2 | edge, < 4 x 2n), vertices (ghost = -1), coordinates: 42 bytes per vertex, 3 700
 //     vertices per side in 152 KB (a 720p frame has 3 100 - 3 400).  Sides that do not fit, or whose vertices coincide (k_arrange hands
 //     those back: which duplicate survives depends on Triangle's randomised quicksort), set the frame's need_host flag and the slot's
-//     worker sends the batch through the host stage instead (jn_api.cpp).
+//     worker sends the batch through the host stage instead (elas_batch.cpp).
 //   * Round 6 — sides beyond one workgroup's LDS (1920x1080: ~11 200 support points a side): the tree is cut at depth C.
 //     k_delaunay_sub runs every subtree below the cut in its own workgroup (the structure of ITS vertices in LDS, 16-bit links relative to
 //     the subtree's first slot) and writes its records, with 32-bit links, and its hull handles to a global scratch; k_delaunay_top runs the

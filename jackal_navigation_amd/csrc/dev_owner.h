@@ -1,4 +1,4 @@
-// dev_owner.h — what one slot of a matcher handle made on the GPU, released in one place (jn_api.cpp, sgm.hip, bm.hip).  Product code.
+// dev_owner.h — what one slot of a matcher handle made on the GPU, released in one place (elas_api.cpp, sgm.hip, bm.hip).  Product code.
 //
 // Every allocation, event and stream a slot makes goes through its DevOwner, which records it; release() gives everything back in reverse
 // order.  A call that fails records nothing and leaves the caller's pointer null, so a slot that fails half-way is released like a whole

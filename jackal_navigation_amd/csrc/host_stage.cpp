@@ -184,7 +184,7 @@ void HostWorker::triangulate_side(int side, const FrameScratch& fs, uint8_t* pay
 }
 
 // Support points of one frame from the GPU's (uc, vc, d) lattice triples: pixel coordinates, plus the corner points when
-// the preset asks for them.  info->nsup counts both (jn_api.cpp adds kCornerPoints to the GPU's count).
+// the preset asks for them.  info->nsup counts both (elas_batch.cpp adds kCornerPoints to the GPU's count).
 static void points_from_list(const HostParams& hp, const int16_t* t, int nsup, std::vector<int32_t>& u, std::vector<int32_t>& v, std::vector<int32_t>& d) {
   const int nlist = hp.add_corners ? nsup - HostWorker::kCornerPoints : nsup, step = hp.step;
   u.resize(nlist); v.resize(nlist); d.resize(nlist);

@@ -49,7 +49,7 @@ class HostWorker {
   // `arrangement` (optional): the alternating-cut arrangement of this side's vertices computed on the GPU (k_arrange); with it
   // only the hull recursion of the triangulation runs here.
   void triangulate_side_from_list(int side, const int16_t* triples, uint8_t* payload, FrameInfo* info, const uint16_t* arrangement = nullptr);
-  // The same split into phases for callers with idle threads (jn_api.cpp decides): coordinates + Delaunay::prepare into
+  // The same split into phases for callers with idle threads (elas_batch.cpp decides): coordinates + Delaunay::prepare into
   // the caller's per-(frame, side) state, then Delaunay::subtree per part on any worker, then Delaunay::finish.
   struct SideState { Delaunay dt; std::vector<int32_t> xs, ys; int parts = 0; };
   void side_prepare(int side, const int16_t* triples, uint8_t* payload, const FrameInfo* info, SideState* st, int want_parts) const;

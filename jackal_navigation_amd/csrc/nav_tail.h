@@ -1,5 +1,5 @@
 // nav_tail.h — what the scan and the navigation tails behind the matchers share (scan.hip, costmap.hip, subpix.hip, ground.hip,
-// localmap.hip, postfilter.hip; the slots of jn_api.cpp and sgm.hip).  Product code.
+// localmap.hip, postfilter.hip; the slots of elas_handle.h and sgm.hip).  Product code.
 //
 // Host side: the calling thread's device scratch, and NavTails — the tails attached to one slot of a handle.
 // Device side (.hip files only): the reprojection and the ground model, cell and bin of a point, the order-preserving double <-> uint64

@@ -304,3 +304,132 @@ void launch_point_cloud(hipStream_t st, const jn_scan_params& sp, const uint8_t*
 }
 
 }  // namespace jnav
+
+// ================================================================================================
+// the C entry points of the node side (include/jn_stereo.h: "seam B2" and the rectification front end)
+#include <cstring>
+
+using namespace jnav;
+
+extern "C" {
+
+void jn_scan_params_default(jn_scan_params* sp, int32_t W, int32_t H) {
+  // K1 / T of calibration/amrl_jackal_webcam_stereo.yml (calibrated at 640x360, point_cloud.cpp:38),
+  // scaled to the working size; Q in the zero-disparity form stereoRectify emits.
+  const double sx = (double)W / 640.0, sy = (double)H / 360.0;
+  const double f = 4.6417933392659904e+02 * sx, cx = 3.2479711799310849e+02 * sx, cy = 1.8685472713963392e+02 * sy;
+  const double Tx = -9.4052586442980660e-02;
+  const double Q[16] = {1, 0, 0, -cx, 0, 1, 0, -cy, 0, 0, 0, f, 0, 0, -1.0 / Tx, 0};
+  memcpy(sp->Q, Q, sizeof(Q));
+  const double XR[9] = {-0.0007962732853436516, -0.2675000227968607, 0.9635575706420958,
+                        -0.9999984502796089, -0.001321509725770019, -0.00119326128710218,
+                        0.001592547981999815, -0.9635569909380592, -0.2674985457970802};
+  memcpy(sp->XR, XR, sizeof(XR));
+  sp->XT[0] = 0; sp->XT[1] = 0; sp->XT[2] = 0.28;
+  sp->crop_offset_x = 0; sp->crop_offset_y = 0;
+  sp->gp_height_thresh = 0.05; sp->gp_angle_thresh = 4. * 3.1415 / 180.; sp->gp_dist_thresh = 1.0;
+  sp->fov_deg = 90.; sp->bins = 90; sp->pi_approx = 3.1415;
+}
+
+jn_status jn_disparity_to_u8(int32_t device, const float* dD, uint8_t* dOut, int64_t n) {
+  if (!dD || !dOut || n < 0) return JN_ERR_INVALID;
+  HIP_TRY(hipSetDevice(device));
+  if (n) launch_to_u8(nullptr, dD, dOut, n);
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
+  return JN_OK;
+}
+
+jn_status jn_build_valid_disp_lut(int32_t device, const jn_scan_params* sp, int32_t W, int32_t H, uint8_t* dLut) {
+  if (!sp || !dLut || W < 1 || H < 1) return JN_ERR_INVALID;
+  HIP_TRY(hipSetDevice(device));
+  launch_valid_lut(nullptr, *sp, W, H, dLut);
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
+  return JN_OK;
+}
+
+static jn_status scan_common(int32_t device, const jn_scan_params* sp, int32_t n, const float* dD, uint8_t* dDisp,
+                             const uint8_t* dLut, int32_t W, int32_t H, double* dBins, double* dMeta) {
+  if (!sp || !dDisp || !dBins || !dMeta || n < 1 || sp->bins < 1 || sp->bins > 1024) return JN_ERR_INVALID;
+  HIP_TRY(hipSetDevice(device));
+  void* extrema = nullptr;                                    // [n][4] uint64
+  HIP_TRY(thread_scratch(device, sizeof(unsigned long long) * 4 * (size_t)n, &extrema));
+  launch_scan(nullptr, *sp, n, dD, dDisp, dLut, W, H, dBins, dMeta, static_cast<unsigned long long*>(extrema));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
+  return JN_OK;
+}
+
+jn_status jn_obstacle_scan(int32_t device, const jn_scan_params* sp, int32_t n, const uint8_t* dDisp, const uint8_t* dLut,
+                           int32_t W, int32_t H, double* dBins, double* dMeta) {
+  if (!dLut) return JN_ERR_INVALID;
+  return scan_common(device, sp, n, nullptr, const_cast<uint8_t*>(dDisp), dLut, W, H, dBins, dMeta);
+}
+
+jn_status jn_obstacle_scan_cloud(int32_t device, const jn_scan_params* sp, int32_t n, const uint8_t* dDisp, int32_t W, int32_t H,
+                                 double* dBins, double* dMeta) {
+  return scan_common(device, sp, n, nullptr, const_cast<uint8_t*>(dDisp), nullptr, W, H, dBins, dMeta);
+}
+
+jn_status jn_disparity_scan(int32_t device, const jn_scan_params* sp, int32_t n, const float* dD, const uint8_t* dLut,
+                            int32_t W, int32_t H, uint8_t* dDispU8, double* dBins, double* dMeta) {
+  if (!dD || !dLut) return JN_ERR_INVALID;
+  return scan_common(device, sp, n, dD, dDispU8, dLut, W, H, dBins, dMeta);
+}
+
+int32_t jn_compact_ranges(const double* bins, int32_t nbins, float* ranges) {
+  int32_t k = 0;
+  for (int i = nbins - 1; i >= 0; i--)                      // point_cloud.cpp:278-282
+    if (bins[i] < JN_SCAN_EMPTY - 1) ranges[k++] = (float)bins[i];
+  return k;
+}
+
+jn_status jn_point_cloud(int32_t device, const jn_scan_params* sp, const uint8_t* dDisp, int32_t W, int32_t H, float* dXyz,
+                         int64_t* count) {
+  if (!sp || !dDisp || !dXyz || !count || W < 1 || H < 1) return JN_ERR_INVALID;
+  HIP_TRY(hipSetDevice(device));
+  void* scratch = nullptr;
+  HIP_TRY(thread_scratch(device, sizeof(long long) * ((size_t)W + 1), &scratch));
+  long long* cols = static_cast<long long*>(scratch);
+  launch_point_cloud(nullptr, *sp, dDisp, W, H, dXyz, cols);
+  long long total = 0;
+  HIP_TRY(hipMemcpy(&total, cols + W, sizeof(long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipGetLastError());
+  *count = total;
+  return JN_OK;
+}
+
+// ---- rectification front end -----------------------------------------------------------------------
+jn_status jn_init_undistort_rectify_map(int32_t device, const double K[9], const double D[5], const double R[9], const double P[12],
+                                        int32_t W, int32_t H, float* dMapX, float* dMapY) {
+  if (!K || !D || !R || !P || !dMapX || !dMapY || W < 1 || H < 1) return JN_ERR_INVALID;
+  // iR = inverse(P[:, :3] * R), by cofactors
+  double M[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) M[3 * i + j] = P[4 * i] * R[j] + P[4 * i + 1] * R[3 + j] + P[4 * i + 2] * R[6 + j];
+  const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
+  const double det = M[0] * c00 + M[1] * c01 + M[2] * c02;
+  if (det == 0.0) return JN_ERR_INVALID;
+  const double id = 1.0 / det;
+  const double iR[9] = {c00 * id, (M[2] * M[7] - M[1] * M[8]) * id, (M[1] * M[5] - M[2] * M[4]) * id,
+                        c01 * id, (M[0] * M[8] - M[2] * M[6]) * id, (M[2] * M[3] - M[0] * M[5]) * id,
+                        c02 * id, (M[1] * M[6] - M[0] * M[7]) * id, (M[0] * M[4] - M[1] * M[3]) * id};
+  HIP_TRY(hipSetDevice(device));
+  launch_undistort_map(nullptr, iR, K, D, W, H, dMapX, dMapY);
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
+  return JN_OK;
+}
+
+jn_status jn_remap_bilinear(int32_t device, int32_t n, const uint8_t* dSrc, int32_t sw, int32_t sh, int32_t spitch, int64_t sstride,
+                            const float* dMapX, const float* dMapY, uint8_t* dDst, int32_t W, int32_t H, int32_t dpitch, int64_t dstride) {
+  if (!dSrc || !dMapX || !dMapY || !dDst || n < 1 || sw < 1 || sh < 1 || W < 1 || H < 1 || spitch < sw || dpitch < W) return JN_ERR_INVALID;
+  HIP_TRY(hipSetDevice(device));
+  launch_remap(nullptr, n, dSrc, sw, sh, spitch, sstride, dMapX, dMapY, dDst, W, H, dpitch, dstride);
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipGetLastError());
+  return JN_OK;
+}
+
+}  // extern "C"

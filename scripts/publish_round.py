@@ -109,7 +109,7 @@ if os.path.exists(fs) and os.path.exists(ws):     # SGM traffic from its own PMC
     published["%s_sgm_pmc_traffic.json" % rnd] = "from %s_sgm_pmc_*.txt" % tag
 manifest = {"tag": tag, "commit": subprocess.run(["git", "-C", root, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip(),
             "sources_sha256": {f: sha(f) for f in ("jackal_navigation_amd/csrc/kernels.hip", "jackal_navigation_amd/csrc/scan.hip", "jackal_navigation_amd/csrc/sgm_sweep.hip", "jackal_navigation_amd/csrc/bm.hip", "jackal_navigation_amd/csrc/bm_mfma.hip", "jackal_navigation_amd/csrc/prefilter.h",
-                                                   "jackal_navigation_amd/csrc/delaunay_gpu.hip", "jackal_navigation_amd/csrc/jn_api.cpp", "bench.py")},
+                                                   "jackal_navigation_amd/csrc/delaunay_gpu.hip", "jackal_navigation_amd/csrc/elas_api.cpp", "jackal_navigation_amd/csrc/elas_batch.cpp", "bench.py")},
             "inputs_newest_mtime": _newest_in, "files": published}
 json.dump(manifest, open(os.path.join(p, "%s_manifest.json" % tag), "w"), indent=1)
 open(os.path.join(p, "CURRENT"), "w").write(tag + "\n")

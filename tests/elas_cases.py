@@ -118,7 +118,7 @@ def prior_edge_betas(gamma=3.0):
 
 
 # ------------------------------------------------------------------ dispatch, restated ------------------------------------------------------------------
-# Only what decides WHICH kernel runs (csrc/kernels.hip launchers, csrc/jn_api.cpp plan_batch / queue_stage_a / queue_post_processing /
+# Only what decides WHICH kernel runs (csrc/kernels.hip launchers, csrc/elas_batch.cpp plan_batch / queue_stage_a / queue_post_processing /
 # queue_stage_b, csrc/delaunay_gpu.hip launch_delaunay), for the FIRST batch of a fresh handle, every frame of which finds support points.
 DT_WHOLE = (152 * 1024 - 64) // 32          # delaunay_gpu_capacity(152 KB): vertices of a side one workgroup's LDS holds
 STRIP_W, TILE_H = 128, 8

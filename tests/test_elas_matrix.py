@@ -87,7 +87,7 @@ HOOK_NAMES = ("JN_SUPPORT_SPLIT", "JN_SUPPORT_SEGMENTS", "JN_FUSE_LIST", "JN_BIN
 
 def test_hook_names_are_the_hooks_builds(jn):
     """what the table treats as a hooks-only knob is read through JN_HOOK_ENV, what it treats as shipped through getenv"""
-    src = open(os.path.join(CSRC, "kernels.hip")).read() + open(os.path.join(CSRC, "jn_api.cpp")).read() + open(os.path.join(CSRC, "delaunay_gpu.hip")).read()
+    src = "".join(open(os.path.join(CSRC, f)).read() for f in ("kernels.hip", "jn_api.cpp", "elas_api.cpp", "elas_batch.cpp", "elas_seams.cpp", "delaunay_gpu.hip"))
     used = {k for c in ec.ALL_CASES for k in c.env}
     for k in used:
         hook, shipped = 'JN_HOOK_ENV("%s")' % k in src, 'getenv("%s")' % k in src.replace("JN_HOOK_ENV(", "hook(")

@@ -1,5 +1,5 @@
 """ThreadSanitizer over the host-stage task pool (csrc/pool.h): several slot threads submit frame
-tasks and frame-side tasks concurrently, exactly as jn_api.cpp's slot workers do; results must equal
+tasks and frame-side tasks concurrently, exactly as elas_batch.cpp's slot workers do; results must equal
 the serial ones.  CPU only (no HIP in pool.h / host_stage / delaunay)."""
 import os
 import subprocess
